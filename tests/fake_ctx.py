@@ -62,6 +62,10 @@ class FakeContext:
     def last_log_stages(self): return dict(walk_ms=30.0, scan_ms=0.1, partition_ms=10.0, reduce_ms=3.0, records=1800, batches=1)
     def read_counters(self): self._log("read_counters", steps=self.steps); return dict(steps=self.steps)
     def read_grid_into(self, buf): self._log("read_grid_into", nbytes=int(np.asarray(buf).nbytes)); return buf
+
+    def read_grid(self):        # every voxel holds the job's (reduced) step count: the dump shows which job it saw
+        self._log("read_grid", steps=self.steps)
+        return np.full(self.shape[::-1], float(self.steps))
     def device_info(self): return dict(name="fake", cus=256, clock_mhz=2400, hbm_bytes=288 * 2 ** 30)
     def close(self): self._log("close")
 

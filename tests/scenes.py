@@ -265,6 +265,43 @@ def obj_in_box(verts, faces, n=40, split_method=0, half=4.0, **kw):
     return prob, ordered, linear, np.array([t.face_index for t in ordered]), scale, shift
 
 
+def write_obj(path, verts, faces, degenerate_every=0):
+    """A triangle mesh as OBJ text that exercises every form src/io.read_obj accepts; reading it back must give verts
+    and faces (plus the zero-area triangles injected below).  Written: comment / mtllib / o lines before the data,
+    vn / vt / s / g / usemtl lines between the vertices and the faces and `usemtl` again every 500 face lines; `v` lines
+    in repr, every 7th in E-notation (both read back bit for bit); each maximal fan run (a, b, c), (a, c, d), (a, d, e) ...
+    as ONE polygon (`f a b c d e ...`); corners as `a`, `a//n`, `a/t/n`, `a/t` in turn, every 3rd polygon with negative
+    (relative) indices, every 5th with a run of blanks after `f`; after every `degenerate_every`-th polygon (0: never) a
+    zero-area quad `f a a b b` (two zero-area fan triangles); no final newline.  Returns (path, injected triangles)."""
+    v = np.asarray(verts, dtype=np.float64)
+    f = np.asarray(faces)
+    nv = len(v)
+    lines = ["# %d vertices, %d triangles" % (nv, len(f)), "mtllib m.mtl", "o obj"]
+    lines += [("v " + " ".join(("%.16E" if k % 7 == 3 else "%r") % float(x) for x in p)) for k, p in enumerate(v)]
+    lines += ["vn 0.0 0.0 1.0", "vt 0.5 0.5", "s off", "g grp", "usemtl m"]
+    polys, k = [], 0
+    while k < len(f):
+        poly = [int(i) for i in f[k]]
+        k += 1
+        while k < len(f) and f[k][0] == poly[0] and f[k][1] == poly[-1]:
+            poly.append(int(f[k][2]))
+            k += 1
+        polys.append(poly)
+    forms = ("%d", "%d//1", "%d/1/1", "%d/1")
+    injected = 0
+    for j, poly in enumerate(polys):
+        idx = [i - nv if j % 3 == 2 else i + 1 for i in poly]
+        lines.append("f" + ("     " if j % 5 == 4 else " ") + " ".join(forms[j % 4] % i for i in idx))
+        if degenerate_every and j % degenerate_every == degenerate_every - 1:
+            lines.append("f %d %d %d %d" % (poly[0] + 1, poly[0] + 1, poly[1] + 1, poly[1] + 1))
+            injected += 2
+        if j % 500 == 499:
+            lines.append("usemtl m")
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines))
+    return str(path), injected
+
+
 def share_an_edge(tri_a, tri_b, tol=1e-9):
     """Two triangles ([3, 3] vertex arrays) with at least two common vertices."""
     common = sum(1 for p in tri_a if np.any(np.all(np.abs(tri_b - p) <= tol * (1.0 + np.abs(p).max()), axis=1)))

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,3 +110,29 @@ def test_bench_self_launches_for_n_greater_than_1(tmp_path):
     bad = subprocess.run([a if a != "tests.fake_ctx:make" else "tests.fake_ctx:no_such_factory" for a in cmd], env=env, cwd=ROOT,
                          capture_output=True, text=True, timeout=240)
     assert bad.returncode != 0 and "no_such_factory" in bad.stderr
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: after the K timed steps rank 0 writes what the LAST one computed (reduced over the ranks), before
+    any later launch reuses its context: float64 .npy files, 64 MB at most, the same files from two runs of one command."""
+    K, W, n = 5, 1, 1000
+    dumps = []
+    for r in range(2):
+        d = tmp_path / ("out%d" % r)
+        run_dir = tmp_path / ("run%d" % r)
+        run_dir.mkdir()
+        out, calls = run_bench(run_dir, ["--inflight", "2", "--steps", str(K), "--warmup", str(W), "--photons", str(n),
+                                         "--dump-outputs", str(d)])
+        files = sorted(os.listdir(d))
+        assert "grid_sample.npy" in files and "counters_steps.npy" in files and all(f.endswith(".npy") for f in files)
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 10 ** 6
+        last = 2 * (281 * n + K - 1)                      # the fake job's steps of the last timed seed, summed over 2 ranks
+        assert arrays["counters_steps.npy"].tolist() == [last] and np.all(arrays["grid_sample.npy"] == last)
+        ops = [(c["op"], c.get("seed")) for c in calls[0]]
+        read = ops.index(("read_grid", None))
+        assert ops.index(("launch", K - 1)) < read < ops.index(("launch", 510))
+        assert not any(c["op"] == "read_grid" for c in calls[1])
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])

@@ -143,7 +143,14 @@ def test_bench_under_the_launcher_keeps_the_plain_rate():
     best_plain, best_launched = max(d["value"] for d in plain), max(d["value"] for d in launched)
     for d in plain + launched:
         assert d["config"]["regime"] == "three_jobs" and d["config"]["serialised_ranks"] == 0, d["config"]
-        assert d["config"]["overlap_factor_min"] > 1.8, d["config"]      # three jobs in flight really were in flight together
+        # the jobs in flight really were in flight together.  On three or more hardware queues every job has one of its
+        # own: > 1.8.  bench.py asks the runtime for 2 (its default is 4), and three jobs then share two queues: measured
+        # on an MI355X, overlap_factor_min 1.562-1.565 plain and 1.489 under the launcher (two runs each): > 1.4
+        queues = int(d["config"]["gpu_max_hw_queues"] or 4)
+        assert d["config"]["overlap_factor_min"] > (1.8 if queues >= 3 else 1.4), d["config"]
+    # ... and the launcher (torch.distributed + RCCL, streams of its own) did not take that overlap away
+    assert min(d["config"]["overlap_factor_min"] for d in launched) >= 0.9 * max(d["config"]["overlap_factor_min"] for d in plain), (
+        [d["config"]["overlap_factor_min"] for d in plain], [d["config"]["overlap_factor_min"] for d in launched])
     assert launched[0]["config"]["reduce"]["backend"] == "nccl" and launched[0]["config"]["reduce"]["calls_rank0"] >= 15
     assert best_launched >= 0.95 * best_plain, (best_plain, best_launched)
 
