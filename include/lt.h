@@ -172,6 +172,8 @@ int lt_set_max_steps(lt_ctx* ctx, uint32_t max_steps);
  *                      streams).  For hosts that keep several jobs in flight: launch each walk at three of the four resident
  *                      workgroups per CU (lt_set_launch_config(3, 256)) and the free quarter of the register file carries the
  *                      reduction of the job in front (bench.py's walk_train regime)
+ *   render_lds_tables  0: lt_render_surface reads the scene tables from global memory even where they fit LDS (tests: the two
+ *                      kernels give the same image bit for bit)
  *   -- taking effect when the mesh tables are next built (lt_set_mesh + launch / query):
  *   march_cells, march_scale_milli   march grid: cells along the longest axis / cell size in 1/1000 of the default
  *   clearance_cells    clearance grid of meshes in LDS: cells along the longest axis
@@ -274,7 +276,8 @@ int lt_reduce_grid(lt_ctx* ctx, void* nccl_comm, int root);
  * LDS (wave-cooperative: lanes march their rays through the grid, the whole wave tests the candidates; built on request for
  * smaller meshes); 3: the same march lane by lane; 4: the BVH front to back -- the child on the ray's side of the split plane
  * first, the reference's order (bvh_new.py:455-458), threaded per direction sign pattern so that it needs no stack: what the
- * surface renderers use.  All five give the same answer bit for bit. */
+ * surface renderers use (a BVH of more than 32767 nodes has no front-to-back tables: 4 then searches it in storage order,
+ * as 1 does).  All five give the same answer bit for bit. */
 int lt_intersect_rays(lt_ctx* ctx, const double* origins, const double* dirs,
                       const double* tmax, size_t n, int use_bvh, int32_t* prim_out,
                       double* t_out);
@@ -343,7 +346,9 @@ int lt_set_lights(lt_ctx* ctx, const lt_point_light* lights, int n);
  * markers the reference writes for unused bounces (:38,66,130).  light_choice
  * [H][W][S][D]: index of the light sample used by the shadow ray of that bounce
  * (the reference draws it with np.random.choice, light_samples.py:38).
- * image [H][W][3] is ACCUMULATED into: += 0.25 * clip(mean colour) (:166). */
+ * image [H][W][3] is ACCUMULATED into: += 0.25 * clip(mean colour) (:166).
+ * Any mesh size: the BVH is searched front to back (lt_intersect_rays form 4), in
+ * storage order where it has more than 32767 nodes. */
 int lt_render_surface(lt_ctx* ctx, int width, int height, int samples, int max_depth,
                       const double camera[3], double f_distance, const double* xs,
                       const double* ys, double* rand_0, const double* rand_1,

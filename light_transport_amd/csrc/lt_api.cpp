@@ -141,7 +141,8 @@ struct lt_ctx {
     struct Knobs {
         long query_min = -1, log_bits2 = -1, log_hot = -1, overlap_walk_bpc = -1, diag_no_tally = -1, log_timing = -1,
              march_cells = -1, march_scale_milli = -1, no_march = -1, no_clearance = -1, no_near_lists = -1,
-             clearance_cells = -1, march_info = -1, force_march = -1, tail_split = -1, part_alone = -1, serial_walks = -1, part_lds = -1;
+             clearance_cells = -1, march_info = -1, force_march = -1, tail_split = -1, part_alone = -1, serial_walks = -1, part_lds = -1,
+             render_lds_tables = -1;
         std::string overlap_pattern;      // LT_OVERLAP_PATTERN (relative sub-batch sizes; tools/pattern_ab.py)
     } knob;
     long* knob_by_name(const char* key)
@@ -151,7 +152,8 @@ struct lt_ctx {
             {"overlap_walk_bpc", &Knobs::overlap_walk_bpc}, {"diag_no_tally", &Knobs::diag_no_tally}, {"log_timing", &Knobs::log_timing},
             {"march_cells", &Knobs::march_cells}, {"march_scale_milli", &Knobs::march_scale_milli}, {"no_march", &Knobs::no_march},
             {"no_clearance", &Knobs::no_clearance}, {"no_near_lists", &Knobs::no_near_lists}, {"clearance_cells", &Knobs::clearance_cells},
-            {"march_info", &Knobs::march_info}, {"force_march", &Knobs::force_march}, {"tail_split", &Knobs::tail_split}, {"part_alone", &Knobs::part_alone}, {"serial_walks", &Knobs::serial_walks}, {"part_lds", &Knobs::part_lds}};
+            {"march_info", &Knobs::march_info}, {"force_march", &Knobs::force_march}, {"tail_split", &Knobs::tail_split}, {"part_alone", &Knobs::part_alone}, {"serial_walks", &Knobs::serial_walks}, {"part_lds", &Knobs::part_lds},
+            {"render_lds_tables", &Knobs::render_lds_tables}};
         for (const auto& t : tab) if (std::strcmp(key, t.k) == 0) return &(knob.*(t.m));
         return nullptr;
     }
@@ -977,7 +979,8 @@ int lt_create(lt_ctx** out, int device_id)
     c->device = device_id;
     {   // the one place the environment is read: LT_QUERY_MIN, LT_LOG_HOT, ... seed the knobs of lt_set_tuning
         static const char* const names[] = {"query_min", "log_bits2", "log_hot", "overlap_walk_bpc", "diag_no_tally", "log_timing", "march_cells",
-                                            "march_scale_milli", "no_march", "no_clearance", "no_near_lists", "clearance_cells", "march_info", "force_march", "tail_split", "part_alone", "serial_walks", "part_lds"};
+                                            "march_scale_milli", "no_march", "no_clearance", "no_near_lists", "clearance_cells", "march_info", "force_march", "tail_split", "part_alone", "serial_walks", "part_lds",
+                                            "render_lds_tables"};
         for (const char* k : names) {
             std::string name = "LT_";
             for (const char* q = k; *q; q++) name += (char)std::toupper((unsigned char)*q);
@@ -1608,12 +1611,9 @@ int stage_in(lt_ctx* c, DevBuf& b, const void* h, size_t bytes)
 }
 }  // namespace
 
-// the link tables of the ctx mesh on the device (rebuilt per call: a few KB; the mesh may have changed)
-static int upload_links(lt_ctx* c)      // (upload_tables has put them on the device with the mesh)
-{
-    if (!c->have_links) return c->fail(LT_E_UNSUPPORTED, "BVH of %zu nodes: the front-to-back order tables hold 16-bit links", c->nodes.size());
-    return LT_OK;
-}
+// the front-to-back link tables of the ctx mesh on the device (upload_tables has put them there with the mesh), or null
+// when the mesh has none (a BVH beyond 32767 nodes: the links are 16-bit) -- d_links may still hold an earlier mesh's
+static const int16_t* mesh_links(const lt_ctx* c) { return c->have_links ? (const int16_t*)c->d_links.p : nullptr; }
 
 int lt_intersect_rays(lt_ctx* c, const double* origins, const double* dirs, const double* tmax, size_t n, int use_bvh,
                       int32_t* prim_out, double* t_out)
@@ -1627,7 +1627,6 @@ int lt_intersect_rays(lt_ctx* c, const double* origins, const double* dirs, cons
     if (c->media.empty()) { lt_medium m = {0, 0, 0, 1}; c->media.push_back(m); }
     int rc = upload_tables(c);
     if (rc) return rc;
-    if (use_bvh == 4 && (rc = upload_links(c))) return rc;
     if ((use_bvh == 2 || use_bvh == 3) && !c->have_march) {      // small meshes have no march grid of their own: build one on request
         if ((rc = build_march_grid(c))) return rc;
         if (!c->have_march) return c->fail(LT_E_UNSUPPORTED, "lt_intersect_rays: no march grid for this mesh");
@@ -1644,7 +1643,7 @@ int lt_intersect_rays(lt_ctx* c, const double* origins, const double* dirs, cons
     HIP_TRY(c, launch_intersect_rays(c->d_tris[0].p, c->d_nodes[0].p, (int)c->med_front.size(), (int)c->nodes.size(),
                                      (const double*)base, (const double*)(base + vb),
                                      tmax ? (const double*)(base + 2 * vb) : nullptr, n, use_bvh, c->have_march ? &c->mgrid : nullptr,
-                                     use_bvh == 4 ? (const int16_t*)c->d_links.p : nullptr, (int32_t*)c->d_scratch_aux.p, (double*)c->d_scratch_out.p, c->stream));
+                                     use_bvh == 4 ? mesh_links(c) : nullptr, (int32_t*)c->d_scratch_aux.p, (double*)c->d_scratch_out.p, c->stream));
     HIP_TRY(c, hipMemcpyAsync(prim_out, c->d_scratch_aux.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(t_out, c->d_scratch_out.p, tb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1794,7 +1793,6 @@ static int render_impl(lt_ctx* c, int variant, int choices, int width, int heigh
     HIP_TRY(c, c->d_lights.ensure(c->lights.size() * sizeof(lt_point_light)));
     HIP_TRY(c, c->d_r0.ensure(n_tab * 8)); HIP_TRY(c, c->d_r1.ensure(n_tab * 8)); HIP_TRY(c, c->d_lc.ensure(n_lc * 4));
     HIP_TRY(c, c->d_img.ensure(n_img * 8)); HIP_TRY(c, c->d_xy.ensure((size_t)(width + height) * 8));
-    if ((rc = upload_links(c))) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_mats.p, c->surf_mats.data(), c->surf_mats.size() * sizeof(lt_surface_material), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_lights.p, c->lights.data(), c->lights.size() * sizeof(lt_point_light), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_r0.p, rand_0, n_tab * 8, hipMemcpyHostToDevice, c->stream));
@@ -1807,7 +1805,7 @@ static int render_impl(lt_ctx* c, int variant, int choices, int width, int heigh
     std::memset(&P, 0, sizeof P);
     P.tris = c->d_tris[0].p; P.nodes = c->d_nodes[0].p;
     P.mats = (const lt_surface_material*)c->d_mats.p; P.lights = (const lt_point_light*)c->d_lights.p;
-    P.links = (const int16_t*)c->d_links.p;
+    P.links = mesh_links(c);      // (null beyond 32767 nodes: the kernels search the BVH in storage order)
     P.n_tris = (int)c->med_front.size(); P.n_nodes = (int)c->nodes.size(); P.n_lights = (int)c->lights.size();
     P.W = width; P.H = height; P.S = samples; P.D = max_depth;
     for (int k = 0; k < 3; k++) P.cam[k] = camera[k];
@@ -1816,6 +1814,7 @@ static int render_impl(lt_ctx* c, int variant, int choices, int width, int heigh
     P.rand_0 = (double*)c->d_r0.p; P.rand_1 = (const double*)c->d_r1.p; P.light_choice = (const int32_t*)c->d_lc.p;
     P.image = (double*)c->d_img.p;
     P.variant = variant; P.choices = choices;
+    P.lds_tables = c->knob.render_lds_tables == 0 ? 0 : 1;
     HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
     HIP_TRY(c, launch_render_surface(P, c->stream));
     HIP_TRY(c, hipEventRecord(c->ev1, c->stream));

@@ -199,7 +199,8 @@ struct RenderParams {
     const void* nodes;   // NodeD<double>
     const lt_surface_material* mats;
     const lt_point_light* lights;
-    const int16_t* links;   // [8][2][n_nodes] front-to-back threading of the BVH per direction sign pattern (nearest_bvh_ordered)
+    const int16_t* links;   // [8][2][n_nodes] front-to-back threading of the BVH per direction sign pattern (nearest_bvh_render);
+                            // null beyond 32767 nodes: the BVH is then searched in storage order
     int n_tris, n_nodes, n_lights;
     int W, H, S, D;
     double cam[3], f_distance;
@@ -211,6 +212,7 @@ struct RenderParams {
     double* image;
     int variant;   // 0 = path_tracing_fix1.trace_path, 1 = path_tracing_old.trace_path
     int choices;   // variant 1: light_choice entries per sample
+    int lds_tables;   // variant 0: 0 = scene tables always in global memory (lt_set_tuning "render_lds_tables"), else in LDS where they fit
 };
 constexpr int kRenderOldMaxDepth = 24;   // frames of the unrolled recursion (variant 1)
 // march grid: exact point-to-mesh distance per cell by a pruned BVH nearest-point query, seeded from a coarse pass

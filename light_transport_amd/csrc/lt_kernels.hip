@@ -530,6 +530,40 @@ LT_DEV void nearest_bvh_walk(const TriD<R>* tris, const NodeD<R>* nodes, int n_n
     else nearest_bvh(tris, nodes, n_nodes, o, d, tmax, prim, t_out);
 }
 
+// the renderers' BVH search: front to back where the mesh has link tables, in storage order (NodeD::skip, as nearest_bvh)
+// where it has none (beyond 32767 nodes) -- ONE loop either way: the render kernels inline their single traversal site,
+// and a second inlined traversal costs them registers.  ANY as in nearest_bvh_ordered.
+template <typename R>
+LT_DEV void nearest_bvh_render(const TriD<R>* tris, const NodeD<R>* nodes, int n_nodes, const int16_t* links, const R* o,
+                               const R* d, R tmax, int& prim, R& t_out, bool ANY = false)
+{
+    int bi = -1; R bt = tmax;
+    const R inv_d[3] = {(R)1 / d[0], (R)1 / d[1], (R)1 / d[2]};  // S/bvh_new.py:418
+    const R slack = box_widen<R>();
+    const int16_t* first = links ? links + ray_octant(d) * 2 * n_nodes : nullptr;
+    const int16_t* after = links ? first + n_nodes : nullptr;
+    int cur = 0;
+    while (cur < n_nodes) {
+        const NodeD<R>* nd = &nodes[cur];
+        const R lo[3] = {nd->lo[0], nd->lo[1], nd->lo[2]};
+        const R hi[3] = {nd->hi[0], nd->hi[1], nd->hi[2]};
+        const int np = nd->n_prims, off = nd->offset;
+        const int next = links ? (int)after[cur] : nd->skip;         // once the subtree of cur is done (or missed)
+        if (box_hit(lo, hi, o, inv_d, bt * slack)) {
+            if (np > 0) {
+                for (int k = 0; k < np; k++) consider(tris, off + k, o, d, bi, bt);
+                if (ANY && bi >= 0) break;
+                cur = next;
+            } else {
+                cur = links ? (int)first[cur] : cur + 1;
+            }
+        } else {
+            cur = next;
+        }
+    }
+    prim = bi; t_out = bi >= 0 ? bt : Mx<R>::inf();
+}
+
 template <typename R>
 LT_DEV void nearest_brute(const TriD<R>* tris, int n_tris, const R* o, const R* d, R tmax,
                           int& prim, R& t_out)
@@ -1796,7 +1830,7 @@ __device__ __forceinline__ bool shadow_direct(const RenderParams& P, const TriD<
     // (the reference takes the nearest hit of the shadow ray and asks whether it lies at mag - EPSILON or beyond, :49-52: the
     // sample is hidden exactly when SOME triangle is hit nearer than that, so the search stops at the first one it finds)
     int sp; double st;
-    nearest_bvh_ordered(tris, nodes, P.n_nodes, links + ray_octant(sd) * 2 * P.n_nodes, so, sd, mag - eps, sp, st, true);
+    nearest_bvh_render(tris, nodes, P.n_nodes, links, so, sd, mag - eps, sp, st, true);
     (void)inf;
     if (sp >= 0) return false;
     const double cos_t = dot3(n, sd);
@@ -1866,8 +1900,8 @@ __device__ __forceinline__ void specular_bounce(const lt_surface_material& M, co
 // the reference's own order of summation (:148-164), so the image is what the sample loop of round 1-3's kernel gave, bit for
 // bit.  (That kernel ran one lane per pixel over all its samples: 90 000 lanes for the notebook's 300 x 300 render, a third of
 // the device's lanes for 50 sequential paths each.)  Pixels with more than 256 samples take several rounds.  The scene tables
-// (triangles, BVH nodes, materials: 7 KB for the notebook's scene) are staged in LDS when they fit 48 KiB (LDS_TABLES); the
-// 2000 point lights (160 KB) and the random tables stay in global memory.
+// (triangles, BVH nodes, materials: 7 KB for the notebook's scene) are staged in LDS when they fit 48 KiB (LDS_TABLES) and
+// lt_set_tuning "render_lds_tables" is not 0; the 2000 point lights (160 KB) and the random tables stay in global memory.
 constexpr int kRenderThreads = 256;
 #ifndef LT_RENDER_WAVES
 #define LT_RENDER_WAVES 4      // waves per SIMD the register allocator leaves room for: 2 (172 VGPRs, no scratch) 7.1 ms, 3 (168 + 12 B)
@@ -1922,7 +1956,7 @@ __global__ void __launch_bounds__(kRenderThreads, LT_RENDER_WAVES) k_render_surf
             for (int bounce = 0;;) {
                 if (!shadow && bounce >= P.D) break;                        // :24-26
                 int prim; double t;
-                nearest_bvh_ordered(tris, nodes, P.n_nodes, links + ray_octant(d) * 2 * P.n_nodes, o, d, shadow ? smag - eps : inf, prim, t, shadow);    // hit_object, :32 / cast_one_shadow_ray
+                nearest_bvh_render(tris, nodes, P.n_nodes, links, o, d, shadow ? smag - eps : inf, prim, t, shadow);    // hit_object, :32 / cast_one_shadow_ray
                 const double r0 = P.rand_0[base + bounce], r1 = P.rand_1[base + bounce];
                 if (!shadow) {
                     if (prim < 0) { mark_unused(P.rand_0, base, bounce, P.D); break; }
@@ -2057,7 +2091,7 @@ __global__ void __launch_bounds__(kOldThreads) k_render_surface_old(const Render
                     const double r0 = P.rand_0[base + f_bounce], r1 = P.rand_1[base + f_bounce];
                     f_r0 = r0;
                     int prim; double t;
-                    nearest_bvh_ordered(tris, nodes, P.n_nodes, P.links + ray_octant(d) * 2 * P.n_nodes, o, d, inf, prim, t);
+                    nearest_bvh_render(tris, nodes, P.n_nodes, P.links, o, d, inf, prim, t);
                     if (prim < 0) { mark_unused(P.rand_0, base, f_bounce, P.D); done = true; }
                     else {
                         const lt_surface_material M = P.mats[prim];
@@ -2161,7 +2195,8 @@ hipError_t launch_render_surface(const RenderParams& P, hipStream_t s)
     const size_t tables = (size_t)P.n_tris * (sizeof(TriD<double>) + sizeof(lt_surface_material)) + (size_t)P.n_nodes * sizeof(NodeD<double>) +
                           (size_t)((16 * P.n_nodes * 2 + 3) / 4) * 4;
     const size_t lds_l = (size_t)kRenderThreads * 3 * sizeof(double);
-    if (tables <= 48 * 1024)
+    // (a mesh without link tables has more than 32767 nodes, 3 MB of tables: never in LDS; the check keeps lds_copy off a null P.links)
+    if (tables <= 48 * 1024 && P.links && P.lds_tables != 0)
         hipLaunchKernelGGL(k_render_surface<true>, dim3((n + ppb - 1) / ppb), dim3(kRenderThreads), lds_l + tables, s, P);
     else
         hipLaunchKernelGGL(k_render_surface<false>, dim3((n + ppb - 1) / ppb), dim3(kRenderThreads), lds_l, s, P);

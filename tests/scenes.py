@@ -320,3 +320,91 @@ def check_hits_against_fixture(prim, t, fix_prim, fix_t, fix_second, tris, rtol=
         assert abs(fix_second[i] - fix_t[i]) <= 1e-9 * fix_t[i], "ray %d: another triangle although the hit is not a tie" % i
         assert share_an_edge(tris[prim[i]], tris[fix_prim[i]]), "ray %d: tie between triangles that share no edge" % i
     return len(diff)
+
+
+# ---------------------------------------------------------------- surface renderers (lt_render_surface / _old)
+RENDER_LDS_BUDGET = 48 * 1024      # launch_render_surface stages the scene tables in LDS up to this many bytes
+
+
+def render_table_bytes(n_tris, n_nodes):
+    """The bytes of scene tables k_render_surface<true> stages in LDS (launch_render_surface): per triangle a TriD<double>
+    (104 B) and an lt_surface_material (64 B), per node a NodeD<double> (64 B) and 8 x 2 int16 links (32 B)."""
+    return n_tris * (104 + 64) + n_nodes * 64 + (16 * n_nodes * 2 + 3) // 4 * 4
+
+
+def cone_mesh():
+    """(vertices, faces) of the notebook's cone (cornell_box.get_cone, 10 triangles)."""
+    tris = cb.get_cone(K.GLASS_MAT)
+    v = np.concatenate([t.vertices3() for t in tris])
+    return v, np.arange(len(v)).reshape(-1, 3)
+
+
+def render_scene(verts, faces, half=7.5, fill=0.8, glass_every=3, n_light_samples=16, seed=3, split_method=0):
+    """A vertex / face mesh in the notebook's open Cornell box (cornell_box.get_cornell_box + get_light_quad, no front
+    wall: the camera looks in), turned so that its thinnest side faces the camera, scaled so that its longest side is
+    `fill` of the box and centred, SAH-built.  Materials reach every branch of both integrators: diffuse walls (coloured
+    left / right, grey floor and ceiling), a MIRROR back wall, the light quad (diffuse, is_light, emission 200), and the
+    object's faces split between GLASS (transmission 1, ior 1.5; every `glass_every`-th face) and dark diffuse ones, which
+    absorb most of what reaches them so that roulette ends deep paths.  Point lights: 2 x n_light_samples samples of the
+    light quad (generate_area_light_samples).
+    Returns dict(mesh (set_mesh arrays), mats [T, 9] rows as oracle.render_surface takes them, lights [L, 10],
+    camera, f_distance, is_object [T] bool, n_tris, n_nodes)."""
+    from light_transport_amd.src.io import triangles_from_mesh
+    from light_transport_amd.src.light_samples import generate_area_light_samples
+    from light_transport_amd.src.material import Material
+    v = np.asarray(verts, dtype=np.float64)
+    thin = int(np.argmin(v.max(axis=0) - v.min(axis=0)))
+    v = np.roll(v, 2 - thin, axis=1)        # (a rotation) its thinnest side towards the camera: the wine glass lies flat
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    scale = fill * 2 * half / float((hi - lo).max())
+    shift = -0.5 * (lo + hi) * scale
+    src = Material(color=K.WHITE, shininess=1, reflection=0.9, ior=1.5, emission=200)
+    box = cb.get_cornell_box(half, K.GLASS_MAT, K.GLASS_MAT, K.GLASS_MAT)
+    lq = cb.get_light_quad(half, src)
+    roles = ["right"] * 2 + ["left"] * 2 + ["mirror"] * 2 + ["grey"] * 10
+    for t, r in zip(box, roles):
+        t.role = r
+    for t in lq:
+        t.role = "light"
+    body = triangles_from_mesh(v, faces, K.GLASS_MAT, scale, shift, drop_degenerate=False)
+    for k, t in enumerate(body):
+        t.role = "glass" if k % glass_every == 0 else "dark"
+    ordered, linear = B.build_linear_bvh(box + lq + body, split_method)
+    row = {  # diffuse[3], emission, ior, transmission, is_diffuse, is_mirror, is_light
+        "right": [0.0, 0.6, 0.0, 0, 1.5, 0, 1, 0, 0], "left": [0.7, 0.0, 0.0, 0, 1.5, 0, 1, 0, 0],
+        "grey": [0.55, 0.55, 0.55, 0, 1.5, 0, 1, 0, 0], "mirror": [0.9, 0.9, 0.9, 0, 1.5, 0, 0, 1, 0],
+        "light": [1.0, 1.0, 1.0, 200, 1.5, 0, 1, 0, 1], "glass": [0.6, 0.7, 0.7, 0, 1.5, 1, 0, 0, 0],
+        "dark": [0.15, 0.2, 0.25, 0, 1.5, 0, 1, 0, 0]}
+    mats = np.array([row[t.role] for t in ordered], dtype=np.float64)
+    np.random.seed(seed)
+    lights = np.array([list(l.source[:3]) + list(l.normal[:3]) + [l.material.emission * x for x in l.material.color.diffuse[:3]]
+                       + [l.total_area] for l in generate_area_light_samples(lq[0], lq[1], src, n_light_samples, 4)])
+    mesh = dict(verts=B.triangles_array(ordered), med_front=-np.ones(len(ordered), np.int32),
+                med_back=-np.ones(len(ordered), np.int32), nodes=B.linear_bvh_arrays(linear))
+    # the screen (x, y in [-1, 1] x [-1 / aspect, 1 / aspect]) one unit in front of a camera just outside the open side:
+    # a 90-degree view in which the object fills the middle and walls, mirror and light show around it
+    return dict(mesh=mesh, mats=mats, lights=lights, camera=np.array([0.0, 0.0, half + 0.5]), f_distance=half - 0.5,
+                is_object=np.array([t.role in ("glass", "dark") for t in ordered]), n_tris=len(ordered),
+                n_nodes=len(mesh["nodes"]["offset"]))
+
+
+def render_tables(W, H, S, D, n_lights, choices=None, seed=0):
+    """Seeded tables of one render: xs [W], ys [H] (np.linspace of the Scene's left..right / top..bottom), rand_0, rand_1
+    [H][W][S][D] and light_choice -- [H][W][S][D] for lt_render_surface, [H][W][S][choices] for lt_render_surface_old.
+    Every entry is an independent draw."""
+    rs = np.random.RandomState(seed)
+    r0, r1 = rs.rand(H, W, S, D), rs.rand(H, W, S, D)
+    lc = rs.randint(0, n_lights, size=(H, W, S, D if choices is None else choices)).astype(np.int32)
+    xs, ys = np.linspace(-1, 1, W), np.linspace(1 / (W / H), -1 / (W / H), H)
+    return xs, ys, r0, r1, lc
+
+
+def camera_rays(sc, xs, ys, rand_0):
+    """The bounce-0 rays of every (pixel, sample) (path_tracing_fix1.py:152-160: the jitter re-uses rand_0[..., 0])."""
+    H, W, S, _ = rand_0.shape
+    jit = rand_0[..., 0]
+    cam = sc["camera"]
+    d = np.stack([xs[None, :, None] + jit / W - cam[0], ys[:, None, None] + jit / H - cam[1],
+                  np.full((H, W, S), sc["f_distance"] - cam[2])], axis=-1).reshape(-1, 3)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return np.broadcast_to(cam, d.shape).copy(), d

@@ -899,6 +899,174 @@ def test_render_scene_object_api(ctx, golden_dir):
     assert img is sc.image and img.shape == (16, 24, 3) and 0 < img.max() <= 0.25 and np.isinf(sc.rand_0).any()
 
 
+# ---------------------------------------------------------------- f2: both renderers against the oracle on meshes of every size
+# mesh in the box (tests/scenes.render_scene) -> (scene tables in LDS for k_render_surface, front-to-back link tables);
+# both follow from the mesh's triangle and node counts and are asserted by every test that relies on them
+RENDER_LADDER = {
+    "cornell": (True, True),           # the notebook's cone: 28 triangles
+    "ico2-below": (True, True),        # tables a few hundred bytes under the 48 KiB budget
+    "ico2-above": (False, True),       # ... and a few hundred bytes over it
+    "ico3": (False, True),             # 1298 triangles
+    "teapot": (False, True),           # G10: 6338 triangles, a deep SAH tree from a real asset
+    "wine-glass": (False, False),      # G10b: 25 364 triangles, more than 32767 nodes -- no 16-bit link tables
+}
+_render_scenes = {}
+
+
+def render_ladder_scene(golden_dir, name, **kw):
+    key = (name,) + tuple(sorted(kw.items()))
+    if key not in _render_scenes:
+        if name == "cornell":
+            v, f = S.cone_mesh()
+        elif name.startswith("ico2-"):
+            v, f = S.icosphere(2)
+            f = f[:123 if name == "ico2-below" else 124]        # a cap of the sphere, sized to straddle the LDS budget
+        elif name == "ico3":
+            v, f = S.icosphere(3)
+        else:
+            from tests.test_oracle_golden import _g10_file
+            g, k = _g10_file(golden_dir, name)
+            v, f = g[k + "_verts"], g[k + "_faces"]
+        _render_scenes[key] = S.render_scene(v, f, **kw)
+    return _render_scenes[key]
+
+
+def render_kernel_of(sc):
+    """(LDS tables, link tables) as launch_render_surface / bvh_octant_links decide them for this scene."""
+    return S.render_table_bytes(sc["n_tris"], sc["n_nodes"]) <= S.RENDER_LDS_BUDGET, sc["n_nodes"] <= 32767
+
+
+def bind_render_scene(ctx, sc):
+    from light_transport_amd import _lib
+    m = sc["mesh"]
+    ctx.set_mesh(m["verts"], m["med_front"], m["med_back"], m["nodes"])
+    ctx._mesh_key = None
+    mats = (_lib.SurfaceMaterial * len(sc["mats"]))()
+    for i, r in enumerate(sc["mats"]):
+        mats[i].diffuse[:] = list(r[:3]); mats[i].emission, mats[i].ior, mats[i].transmission = r[3], r[4], r[5]
+        mats[i].is_diffuse, mats[i].is_mirror, mats[i].is_light = int(r[6]), int(r[7]), int(r[8])
+    lights = (_lib.PointLight * len(sc["lights"]))()
+    for i, r in enumerate(sc["lights"]):
+        lights[i].source[:] = list(r[:3]); lights[i].normal[:] = list(r[3:6]); lights[i].radiance[:] = list(r[6:9])
+        lights[i].total_area = r[9]
+    ctx.set_surface_materials(mats); ctx.set_lights(lights)
+
+
+def render_both(ctx, sc, W, H, Sm, D, old=False, seed=0, choices=7):
+    """One render of the bound scene on the device and in the oracle from the same seeded tables: the images and the
+    +inf markers in rand_0 must agree (the walks' tolerance: |d| <= 1e-12 + 1e-9 |E|, zero pixels outside; markers
+    exact), and every entry the render did not mark is returned unchanged.  -> (image, rand_0 after, tables)"""
+    xs, ys, r0, r1, lc = S.render_tables(W, H, Sm, D, len(sc["lights"]), choices if old else None, seed)
+    r0g, r0o = r0.copy(), r0.copy()
+    img = np.full((H, W, 3), 9.0) if old else np.zeros((H, W, 3))       # old overwrites the image, fix1 adds to it
+    imgo = np.zeros((H, W, 3))
+    ctx.render_surface(sc["camera"], sc["f_distance"], xs, ys, r0g, r1, lc, img, old=old)
+    osc = O.OracleScene([(0, 0, 0, 1)], (1, 1, 1), (0, 0, 0), (1, 1, 1), mesh=sc["mesh"])
+    O.render_surface(osc, sc["mats"], sc["lights"], sc["camera"], sc["f_distance"], xs, ys, r0o, r1, lc, imgo, old=old)
+    np.testing.assert_allclose(img, imgo, rtol=1e-9, atol=1e-12)
+    marks = np.isinf(r0o)
+    assert np.array_equal(np.isinf(r0g), marks)
+    assert np.array_equal(r0g[~marks], r0[~marks])
+    return img, r0g, (xs, ys, r0, r1, lc)
+
+
+@pytest.mark.parametrize("variant", ["fix1", "old"])
+@pytest.mark.parametrize("name", list(RENDER_LADDER))
+def test_surface_render_across_mesh_sizes(ctx, golden_dir, name, variant):
+    """lt_render_surface (k_render_surface, tables in LDS or in global memory) and lt_render_surface_old against the
+    oracle's render on the same tables, from the 28-triangle cone to the 25 364-triangle wine glass whose BVH is too
+    large for the front-to-back link tables (the renderers then search it in storage order).  Materials take every
+    branch: diffuse, mirror, glass, light.  The object is checked to fill a real share of the picture."""
+    sc = render_ladder_scene(golden_dir, name)
+    lds, links = render_kernel_of(sc)
+    assert (lds, links) == RENDER_LADDER[name], (S.render_table_bytes(sc["n_tris"], sc["n_nodes"]), sc["n_nodes"])
+    bind_render_scene(ctx, sc)
+    W, H, Sm, D = 24, 16, 2, 6
+    img, r0, (xs, ys, r0_in, r1, lc) = render_both(ctx, sc, W, H, Sm, D, old=(variant == "old"), seed=11)
+    o, d = S.camera_rays(sc, xs, ys, r0_in)
+    p, _ = ctx.intersect_rays(o, d, None, 0)
+    assert np.mean((p >= 0) & sc["is_object"][np.maximum(p, 0)]) >= 0.1, "the camera hardly sees the object"
+    assert img.sum() > 1 and np.isinf(r0).any() and not np.isinf(r0).all()
+    if variant == "fix1":       # the image is accumulated into (:166): a second render adds the same again
+        img2 = img.copy()
+        ctx.render_surface(sc["camera"], sc["f_distance"], xs, ys, r0_in.copy(), r1, lc, img2)
+        np.testing.assert_allclose(img2, 2 * img, rtol=1e-9, atol=1e-12)
+
+
+@pytest.mark.parametrize("D", [1, 6])
+@pytest.mark.parametrize("WH", [(1, 1), (13, 7), (300, 1)], ids=lambda wh: "%dx%d" % wh)
+@pytest.mark.parametrize("Sm", [1, 3, 256, 300])
+def test_surface_render_launch_shapes(ctx, golden_dir, Sm, WH, D):
+    """k_render_surface's split of the work -- chunk = min(S, 256) samples of a pixel per round, 256 / chunk pixels per
+    workgroup, one owner lane per pixel adding its samples -- at one sample, at sample counts that do not divide 256,
+    beyond 256 (two rounds, one pixel per workgroup) and at pixel counts that are no multiple of the pixels per workgroup,
+    against the oracle (tables in global memory, links present)."""
+    sc = render_ladder_scene(golden_dir, "ico3")
+    assert render_kernel_of(sc) == (False, True)
+    bind_render_scene(ctx, sc)
+    W, H = WH
+    img, r0, _ = render_both(ctx, sc, W, H, Sm, D, seed=100 * Sm + W + D)
+    assert img.sum() > 0
+
+
+@pytest.mark.parametrize("D", [1, 24])
+def test_recursive_render_shallowest_and_deepest(ctx, golden_dir, D):
+    """lt_render_surface_old at max_depth 1 and at kRenderOldMaxDepth = 24, where the frame stack takes 137 KiB of LDS
+    (the largest the kernel allows), against the oracle's real recursion on the 1298-triangle sphere."""
+    sc = render_ladder_scene(golden_dir, "ico3")
+    assert render_kernel_of(sc)[1]
+    bind_render_scene(ctx, sc)
+    img, r0, _ = render_both(ctx, sc, 16, 8, 2, D, old=True, seed=7 + D, choices=5)
+    assert img.sum() > 0.1
+
+
+@pytest.mark.parametrize("name", ["cornell", "ico2-below"])
+def test_render_lds_tables_knob_changes_nothing(ctx, golden_dir, name):
+    """lt_set_tuning("render_lds_tables", 0) makes lt_render_surface read the scene tables from global memory
+    (k_render_surface<false>) where they would be staged in LDS: the two kernels differ only in where the tables live,
+    so the images and markers are bit-identical -- the LDS kernel is pinned by G8, the global one to it."""
+    sc = render_ladder_scene(golden_dir, name)
+    assert render_kernel_of(sc) == (True, True)
+    bind_render_scene(ctx, sc)
+    img, r0, (xs, ys, r0_in, r1, lc) = render_both(ctx, sc, 24, 16, 3, 6, seed=31)
+    img_g, r0_g = np.zeros_like(img), r0_in.copy()
+    with ctx.tuning(render_lds_tables=0):
+        ctx.render_surface(sc["camera"], sc["f_distance"], xs, ys, r0_g, r1, lc, img_g)
+    assert np.array_equal(img_g, img) and np.array_equal(r0_g, r0)
+
+
+@pytest.mark.parametrize("name", list(RENDER_LADDER))
+def test_front_to_back_intersect_on_every_mesh(ctx, golden_dir, name):
+    """lt_intersect_rays form 4 (the renderers' front-to-back search; the storage-order BVH where the mesh has no link
+    tables) equals brute force -- prim and t exactly -- on every mesh of the ladder, with no reach, a random reach, and
+    the reach set exactly at (the hit is excluded: t < tmax) and one ulp past each ray's nearest hit."""
+    sc = render_ladder_scene(golden_dir, name)
+    assert render_kernel_of(sc)[1] == RENDER_LADDER[name][1]
+    m = sc["mesh"]
+    ctx.set_mesh(m["verts"], m["med_front"], m["med_back"], m["nodes"])
+    ctx._mesh_key = None
+    rs = np.random.RandomState(17)
+    n = 20000
+    o = rs.uniform(-7.0, 7.0, size=(n, 3))
+    d = rs.normal(size=(n, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+    tgt = m["verts"][rs.randint(0, sc["n_tris"], n // 2)].mean(axis=1)      # half the rays aimed at a triangle's centre
+    d[: n // 2] = tgt - o[: n // 2]; d[: n // 2] /= np.linalg.norm(d[: n // 2], axis=1, keepdims=True)
+    p0, t0 = ctx.intersect_rays(o, d, None, 0)
+    hit = p0 >= 0
+    assert hit.mean() > 0.5 and np.mean(sc["is_object"][p0[hit]]) > 0.2
+    reach = rs.exponential(3.0, n)
+    at = np.where(hit, t0, reach)
+    past = np.where(hit, np.nextafter(t0, np.inf), reach)
+    for tm in (None, reach, at, past):
+        pb, tb = ctx.intersect_rays(o, d, tm, 0)
+        p4, t4 = ctx.intersect_rays(o, d, tm, 4)
+        np.testing.assert_array_equal(p4, pb); np.testing.assert_array_equal(t4, tb)
+        if tm is at:
+            assert not np.any(pb[hit] == p0[hit])         # the nearest hit is just out of reach ...
+        if tm is past:
+            np.testing.assert_array_equal(pb, p0); np.testing.assert_array_equal(tb, t0)     # ... and just within it
+
+
 # ---------------------------------------------------------------- f4: light sub-path vertices
 @pytest.mark.parametrize("name", ["two_layer", "cornell"])
 def test_light_subpath_vertices(ctx, name):
