@@ -139,6 +139,13 @@ int lt_set_mesh(lt_ctx* ctx, const double* verts, const int32_t* med_front,
  * the Python mirror's (light_transport_amd/src/bvh_new.py build_bvh / flatten_bvh) node for node. */
 int lt_build_bvh(const double* verts, int n_tris, int split_method, int32_t* order_out, lt_bvh_node* nodes_out,
                  int max_nodes, int* n_nodes_out);
+/* The tables a layered slab hands its walk kernels, built on the host exactly as lt_launch builds them.  Pure host code: no ctx,
+ * no device.  f32 != 0: walk precision float (every output then holds floats), else double.  media_out [n_media][12]: the
+ * per-medium record (mu_t, 1/mu_t, absorb, g, n, 1-g^2, 1+g^2, 1/(2g), dep, 1-g, 2g, 0); zb_out [n_layers + 1]: the bounds in
+ * walk precision; rec_out [n_layers][12]: the per-layer step record the slab walk reads -- copies of its medium's values and
+ * its own two bounds: (mu_t, 1/mu_t, z_lo, z_hi, absorb, dep, 2g, 1-g, 1-g^2, 1+g^2, 1/(2g), n). */
+int lt_layer_records(const lt_medium* media, int n_media, int quantity, const double* z_bounds, const int32_t* medium_idx,
+                     int n_layers, int f32, void* media_out, void* zb_out, void* rec_out);
 /* voxel grid (tally) -- role of Scene.image (scene.py:66).  C-order
  * [nz][ny][nx]; allocates and zeroes the device grid and the counters. */
 int lt_set_grid(lt_ctx* ctx, int nx, int ny, int nz, const double origin[3],

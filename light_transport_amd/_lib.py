@@ -30,6 +30,7 @@ SYMBOLS = [
     "lt_set_surface_materials", "lt_set_lights", "lt_render_surface", "lt_set_vertex_capture", "lt_read_vertices",
     "lt_set_tally_mode", "lt_last_log_stages", "lt_reserve_log", "lt_render_surface_old", "lt_set_overlap", "lt_last_log_hot_tiles",
     "lt_last_log_info", "lt_set_tally_quantity", "lt_set_tuning", "lt_mesh_accel_info", "lt_build_bvh",
+    "lt_layer_records",
 ]
 
 # lt_vertex as a NumPy record (112 bytes, same layout as the C struct)
@@ -59,6 +60,21 @@ def build_bvh_arrays(verts, split_method=1):
     if rc:
         raise LtError("lt_build_bvh failed (%d): needs >= 1 triangle with finite vertices and split_method 0 or 1" % rc)
     return order, nodes[:nn.value]
+
+
+def layer_records(media, z_bounds, medium_idx, quantity=0, f32=False):
+    """lt_layer_records (host C++, no device): (media_table [M, 12], zb [L + 1], layer_records [L, 12]) in walk precision, as a
+    layered slab's walk kernels get them (field order: lt.h)."""
+    arr = (Medium * len(media))(*[Medium(*map(float, m)) for m in media])
+    zb = _f64(z_bounds)
+    mi = np.ascontiguousarray(medium_idx, dtype=np.int32)
+    dt = np.float32 if f32 else np.float64
+    m_out, z_out, r_out = np.zeros((len(media), 12), dt), np.zeros(zb.size, dt), np.zeros((mi.size, 12), dt)
+    rc = lib().lt_layer_records(arr, C.c_int(len(media)), C.c_int(int(quantity)), _dp(zb), _ip(mi), C.c_int(mi.size), C.c_int(int(f32)),
+                                m_out.ctypes.data_as(C.c_void_p), z_out.ctypes.data_as(C.c_void_p), r_out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise LtError("lt_layer_records failed (%d): needs len(z_bounds) == len(medium_idx) + 1 and medium indices inside the media" % rc)
+    return m_out, z_out, r_out
 
 
 class Medium(C.Structure):

@@ -118,7 +118,7 @@ struct lt_ctx {
     int blocks_per_cu = 0, threads_per_block = 0;
 
     // device buffers
-    DevBuf d_media[2], d_zb[2], d_if[2], d_lm, d_tris[2], d_nodes[2];  // [0]=f64, [1]=f32
+    DevBuf d_media[2], d_zb[2], d_if[2], d_lay[2], d_lm, d_tris[2], d_nodes[2];  // [0]=f64, [1]=f32
     DevBuf d_grid, d_counters, d_head, d_table, d_scratch_in, d_scratch_out, d_scratch_aux;
     DevBuf d_mats, d_lights, d_r0, d_r1, d_lc, d_img, d_xy, d_vtx, d_vcnt, d_clear, d_job, d_gridx[kMaxLanes - 1];   // d_gridx: private grids of lanes 1, 2
     int cn[3] = {0, 0, 0};
@@ -204,6 +204,20 @@ static bool bvh_octant_links(const std::vector<lt_bvh_node>& nd, std::vector<int
         }
     }
     return true;
+}
+
+// Every stream of the library (a ctx's own, its lanes', its tail kernels') is created at the device's GREATEST stream priority.
+// Not for the priority: the runtime keeps one pool of hardware queues per priority level, so the library's streams share
+// queues only with one another -- never with the host program's streams.  A host that reduces every job's grid with RCCL
+// (torch's process group: a communication stream that WAITS for the job's end) otherwise had that wait parked in a queue it
+// shared with another job's stream, whose kernels stood behind it: three jobs in flight overlapped 1.6-fold under the
+// launcher where a plain run reaches 2.6-2.8 on four hardware queues (82.6 against 96e9 photon-steps/s); with pools of their
+// own 2.5-2.7-fold, 93.4-94.3e9.  A plain run is unchanged (profiles/r05a_layer_record_ab.log).
+static hipError_t create_stream(hipStream_t* s)
+{
+    int least = 0, greatest = 0;
+    hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+    return e != hipSuccess ? e : hipStreamCreateWithPriority(s, hipStreamNonBlocking, greatest);
 }
 
 #define CHECK_CTX(c) do { if (!(c)) return LT_E_INVALID; } while (0)
@@ -302,6 +316,17 @@ void fill_ifaces(const lt_ctx* c, std::vector<IfD<R>>& out)
         out[(size_t)k].n_up = up; out[(size_t)k].n_dn = dn;
         out[(size_t)k].nr_down = up / dn; out[(size_t)k].nr_up = dn / up;
     }
+}
+
+// layer records of a layered slab (LayD) from the media table just filled and the ctx's bounds
+template <typename R>
+void fill_layers(const lt_ctx* c, const std::vector<MedD<R>>& media, std::vector<LayD<R>>& out)
+{
+    const std::vector<R> zb(c->z_bounds.begin(), c->z_bounds.end());      // narrowed as the zb table is
+    out.assign(c->layer_medium.size(), LayD<R>());
+    for (int32_t m : c->layer_medium)      // (an index beyond the media table is refused by lt_launch; this only keeps the reads in bounds)
+        if (m < 0 || (size_t)m >= media.size()) return;
+    fill_layer_records(media.data(), zb.data(), c->layer_medium.data(), (int)out.size(), out.data());
 }
 
 template <typename T>
@@ -448,6 +473,7 @@ int upload_tables(lt_ctx* c)
     std::vector<MedD<double>> m64; std::vector<MedD<float>> m32;
     std::vector<double> z64; std::vector<float> z32;
     std::vector<IfD<double>> i64; std::vector<IfD<float>> i32;
+    std::vector<LayD<double>> y64; std::vector<LayD<float>> y32;
     std::vector<TriD<double>> t64; std::vector<TriD<float>> t32;
     std::vector<NodeD<double>> n64; std::vector<NodeD<float>> n32;
     std::vector<int16_t> links16;
@@ -458,6 +484,11 @@ int upload_tables(lt_ctx* c)
         fill_ifaces(c, i64); fill_ifaces(c, i32);
         if ((rc = upload(c, c->d_if[0], i64))) return rc;
         if ((rc = upload(c, c->d_if[1], i32))) return rc;
+        // the slab walk's per-layer step records: copies of the media fields and the bounds, so they follow BOTH tables
+        // (whichever of lt_set_media / lt_set_layers / lt_set_tally_quantity came last has marked one of them dirty)
+        fill_layers(c, m64, y64); fill_layers(c, m32, y32);
+        if ((rc = upload(c, c->d_lay[0], y64))) return rc;
+        if ((rc = upload(c, c->d_lay[1], y32))) return rc;
     }
     if (!c->tables_dirty) {      // only the media table changed (lt_set_tally_quantity): the geometry tables stay
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -796,7 +827,7 @@ int run_log_plan(LogRun& R, const LogPlan& plan, uint64_t offset, int* n_batches
         const size_t gb = c->n_vox() * c->grid_elem();
         HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));
         for (int l = 1; l < plan.lanes; l++) {
-            if (!c->lanes[l].stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->lanes[l].stream, hipStreamNonBlocking));
+            if (!c->lanes[l].stream) HIP_TRY(c, create_stream(&c->lanes[l].stream));
             HIP_TRY(c, hipStreamWaitEvent(c->lanes[l].stream, c->ev_fork, 0));      // (d_gridx: allocated by plan_log)
             HIP_TRY(c, hipMemsetAsync(c->d_gridx[l - 1].p, 0, gb, c->lanes[l].stream));
         }
@@ -870,7 +901,7 @@ int run_log_plan(LogRun& R, const LogPlan& plan, uint64_t offset, int* n_batches
             P.dump_max = c->knob.tail_split > 1 ? (uint32_t)std::min<long>(c->knob.tail_split, (long)kDumpPoolLanes) : kDumpMaxLanes;
             HIP_TRY(c, ln.pool.ensure(cap * (R.v.f32 ? sizeof(SurvD<float>) : sizeof(SurvD<double>))));
             HIP_TRY(c, ln.pool_n.ensure(4));
-            if (!ln.tail_stream) HIP_TRY(c, hipStreamCreateWithFlags(&ln.tail_stream, hipStreamNonBlocking));
+            if (!ln.tail_stream) HIP_TRY(c, create_stream(&ln.tail_stream));
             if (!ln.ev_bulk) HIP_TRY(c, hipEventCreateWithFlags(&ln.ev_bulk, hipEventDisableTiming));
             if (!ln.ev_tail) HIP_TRY(c, hipEventCreateWithFlags(&ln.ev_tail, hipEventDisableTiming));
             HIP_TRY(c, hipMemsetAsync(ln.pool_n.p, 0, 4, s));
@@ -954,6 +985,21 @@ bool bvh_is_valid(const std::vector<lt_bvh_node>& n, int n_tris, int* max_depth)
     return visited == n.size();
 }
 
+// lt_layer_records: the tables of a layered slab in walk precision R, as upload_tables builds them
+template <typename R>
+void layer_records_out(const std::vector<lt_medium>& media, int quantity, const double* z_bounds, const int32_t* medium_idx, int n_layers,
+                       void* media_out, void* zb_out, void* rec_out)
+{
+    static_assert(sizeof(MedD<R>) == 12 * sizeof(R) && sizeof(LayD<R>) == 12 * sizeof(R), "lt_layer_records: 12 values per record");
+    std::vector<MedD<R>> m; fill_media(media, quantity, m);
+    const std::vector<R> zb(z_bounds, z_bounds + n_layers + 1);
+    std::vector<LayD<R>> y((size_t)n_layers);
+    fill_layer_records(m.data(), zb.data(), medium_idx, n_layers, y.data());
+    std::memcpy(media_out, m.data(), m.size() * sizeof(MedD<R>));
+    std::memcpy(zb_out, zb.data(), zb.size() * sizeof(R));
+    std::memcpy(rec_out, y.data(), y.size() * sizeof(LayD<R>));
+}
+
 }  // namespace
 
 extern "C" {
@@ -999,7 +1045,7 @@ int lt_create(lt_ctx** out, int device_id)
         size_t quarter = c->prop.totalGlobalMem / 4;
         c->log_budget = c->default_log_budget = quarter < ((size_t)64 << 30) ? quarter : ((size_t)64 << 30);
     }
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = create_stream(&c->stream);
     c->lanes[0].stream = c->stream;      // (lane 1's stream is created when a launch first overlaps: a process's streams
                                          //  share GPU_MAX_HW_QUEUES hardware queues, idle ones included)
     if (e == hipSuccess) e = hipEventCreate(&c->ev0);
@@ -1024,7 +1070,7 @@ int lt_destroy(lt_ctx* c)
     if (!c) return LT_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (int i = 0; i < 2; i++) { c->d_media[i].release(); c->d_zb[i].release(); c->d_if[i].release(); c->d_tris[i].release(); c->d_nodes[i].release(); }
+    for (int i = 0; i < 2; i++) { c->d_media[i].release(); c->d_zb[i].release(); c->d_if[i].release(); c->d_lay[i].release(); c->d_tris[i].release(); c->d_nodes[i].release(); }
     c->d_lm.release(); c->d_grid.release(); c->d_counters.release(); c->d_head.release(); c->d_table.release();
     c->d_scratch_in.release(); c->d_scratch_out.release(); c->d_scratch_aux.release();
     c->d_mats.release(); c->d_lights.release(); c->d_r0.release(); c->d_r1.release(); c->d_lc.release();
@@ -1063,6 +1109,17 @@ int lt_set_media(lt_ctx* c, const lt_medium* media, int n)
     c->media.assign(media, media + n);
     c->scene_changed();
     c->tables_dirty = true;
+    return LT_OK;
+}
+
+int lt_layer_records(const lt_medium* media, int n_media, int quantity, const double* z_bounds, const int32_t* medium_idx,
+                     int n_layers, int f32, void* media_out, void* zb_out, void* rec_out)
+{
+    if (!media || n_media <= 0 || !z_bounds || !medium_idx || n_layers <= 0 || !media_out || !zb_out || !rec_out) return LT_E_INVALID;
+    for (int l = 0; l < n_layers; l++) if (medium_idx[l] < 0 || medium_idx[l] >= n_media) return LT_E_INVALID;
+    const std::vector<lt_medium> m(media, media + n_media);
+    if (f32) layer_records_out<float>(m, quantity, z_bounds, medium_idx, n_layers, media_out, zb_out, rec_out);
+    else layer_records_out<double>(m, quantity, z_bounds, medium_idx, n_layers, media_out, zb_out, rec_out);
     return LT_OK;
 }
 
@@ -1236,7 +1293,7 @@ int lt_launch(lt_ctx* c, uint64_t n_photons, uint64_t photon_offset, uint64_t se
     P.head = (unsigned long long*)c->d_head.p;
     P.n_photons = n_photons; P.photon_offset = photon_offset; P.seed = seed;
     const int pi = v.f32 ? 1 : 0;
-    P.media = c->d_media[pi].p; P.zb = c->d_zb[pi].p; P.ifaces = c->d_if[pi].p; P.layer_medium = (const int32_t*)c->d_lm.p;
+    P.media = c->d_media[pi].p; P.zb = c->d_zb[pi].p; P.ifaces = c->d_if[pi].p; P.layers = c->d_lay[pi].p; P.layer_medium = (const int32_t*)c->d_lm.p;
     P.tris = c->d_tris[pi].p; P.nodes = c->d_nodes[pi].p; P.links = c->have_mesh && c->have_links ? (const int16_t*)c->d_links.p : nullptr;
     P.n_media = n_media;
     P.n_layers = c->have_layers ? (int)c->layer_medium.size() : 0;

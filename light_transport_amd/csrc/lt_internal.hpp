@@ -29,6 +29,34 @@ struct IfD {
     R nr_down, nr_up;    // n1 / n2 for a photon travelling down (n_up / n_dn) and up (n_dn / n_up)
 };
 
+// Everything a step of the slab walk reads about the layer it is in, as ONE record indexed by the layer: the medium's constants
+// (copies of the MedD fields, bit for bit -- no layer -> medium indirection in front of the free path) and the layer's own two
+// bounds (zb[l], zb[l + 1]).  Values that are used together share a 16-byte quad (pairs in f64, whole quads in f32), so a
+// step fetches the record with six wide LDS reads (three in f32) instead of a dependent index read and seven narrow ones.
+// Built on the host by fill_layer_records (lt_api.cpp) whenever the media or the layers change.
+template <typename R>
+struct alignas(16) LayD {
+    R mu_t, inv_mu_t;        // free path
+    R z_lo, z_hi;            // the layer's bounds: the step takes z_hi when uz > 0, z_lo otherwise
+    R absorb, dep;           // drop
+    R two_g, one_m_g;        // Henyey-Greenstein: denominator (two_g == 0: isotropic) ...
+    R one_m_g2, one_p_g2;    // ... numerator and offset ...
+    R inv_2g, n;             // ... and scale; the refractive index (the interface table carries it for the slab's own events)
+};
+static_assert(sizeof(LayD<double>) == 96 && sizeof(LayD<float>) == 48, "LayD: a whole number of 16-byte quads");
+// (host only, no device needed) the record of every layer from the media / bounds tables the kernels already get
+template <typename R>
+inline void fill_layer_records(const MedD<R>* media, const R* zb, const int32_t* layer_medium, int n_layers, LayD<R>* out)
+{
+    for (int l = 0; l < n_layers; l++) {
+        const MedD<R>& m = media[layer_medium[l]];
+        LayD<R>& r = out[l];
+        r.mu_t = m.mu_t; r.inv_mu_t = m.inv_mu_t; r.z_lo = zb[l]; r.z_hi = zb[l + 1];
+        r.absorb = m.absorb; r.dep = m.dep; r.two_g = m.two_g; r.one_m_g = m.one_m_g;
+        r.one_m_g2 = m.one_m_g2; r.one_p_g2 = m.one_p_g2; r.inv_2g = m.inv_2g; r.n = m.n;
+    }
+}
+
 // Triangle record: role of PreComputedTriangle (primitives.py:99-112).
 template <typename R>
 struct TriD {
@@ -117,6 +145,7 @@ struct WalkParams {
     const void* media;
     const void* zb;
     const void* ifaces;         // IfD<R>[n_layers + 1]
+    const void* layers;         // LayD<R>[n_layers]: the slab walk's per-layer step records
     const int32_t* layer_medium;
     const void* tris;
     const void* nodes;

@@ -280,7 +280,17 @@ LT_DEV void sincos_small_f64(double x, double* sn, double* cs)
 
 // The same two functions from the RAW 32-bit draw k (the uniform is (k + 1) 2^-32): exponent, table cell and remainder come out
 // of integer shifts instead of frexp / ldexp / rint in f64 -- ~5 f64 operations less each, and no conversion of the uniform.
-LT_DEV double neg_log_raw(unsigned k, const double* T)
+// (in two halves: the table cell of a draw -- its address follows from the draw alone, so the slab walk reads it as soon as the
+// draw exists -- and the rest, given the cell; neg_log_raw / sincos_turn_raw are the two back to back)
+LT_DEV double2 neg_log_cell(unsigned k, const double* T)
+{
+    const unsigned n = k + 1u;
+    const unsigned nm = n << (__clz((int)n) & 31);
+    const unsigned sh = 24u + (nm >= 0xC0000000u ? 1u : 0u);
+    const unsigned j = ((nm >> (sh - 1u)) + 1u) >> 1;    // 96 .. 192 (n = 0, one draw in 2^32: j = 0 -- a cell in front of the table whose value is not used)
+    return *reinterpret_cast<const double2*>(T + 2 * ((int)j - 96));
+}
+LT_DEV double neg_log_raw(unsigned k, const double2 Tj)
 {
     const unsigned n = k + 1u;                           // 0 stands for 2^32: the uniform is 1, -ln is 0
     const int lz = __clz((int)n);
@@ -290,7 +300,6 @@ LT_DEV double neg_log_raw(unsigned k, const double* T)
     const unsigned j = ((nm >> (sh - 1u)) + 1u) >> 1;    // rint(t): the cell's centre, 96 .. 192
     const int dint = (int)(nm - (j << sh));              // (t - j) 2^sh, exact (modular arithmetic covers j 2^sh = 2^32)
     const double d = __builtin_ldexp((double)dint, -(int)sh);
-    const double2 Tj = *reinterpret_cast<const double2*>(T + 2 * ((int)j - 96));
     const double r = d * Tj.x;
     double p = 1.0 / 7.0;
     p = fma_k(p, r, -1.0 / 6.0); p = fma_k(p, r, 1.0 / 5.0); p = fma_k(p, r, -0.25); p = fma_k(p, r, 1.0 / 3.0);
@@ -300,7 +309,13 @@ LT_DEV double neg_log_raw(unsigned k, const double* T)
     const double v = -fma_mk(de, 6.93147180369123816490e-01, fma_mk(de, 1.90821492927058770002e-10, lnm));
     return n == 0u ? 0.0 : v;
 }
-LT_DEV void sincos_turn_raw(unsigned k, const double* T, double* sn, double* cs)
+LT_DEV double neg_log_raw(unsigned k, const double* T) { return neg_log_raw(k, neg_log_cell(k, T)); }
+LT_DEV double2 sincos_turn_cell(unsigned k, const double* T)
+{
+    const unsigned iq = (((k + 1u) >> 25) + 1u) >> 1;
+    return *reinterpret_cast<const double2*>(T + 2 * (kLnTabEntries + (int)(iq & (unsigned)(kScTabEntries - 1))));
+}
+LT_DEV void sincos_turn_raw(unsigned k, const double2 Ti, double* sn, double* cs)
 {
     const unsigned n = k + 1u;                           // (n = 0 stands for a full turn: cell 0, remainder 0 -- nothing to special-case)
     const unsigned iq = ((n >> 25) + 1u) >> 1;           // rint(64 xi)
@@ -316,10 +331,10 @@ LT_DEV void sincos_turn_raw(unsigned k, const double* T, double* sn, double* cs)
     pc = fma_k(pc, z, 4.1666666666666666667e-02);
     pc = __builtin_fma(pc, z, -0.5);
     const double cd = __builtin_fma(pc, z, 1.0);
-    const double2 Ti = *reinterpret_cast<const double2*>(T + 2 * (kLnTabEntries + (int)(iq & (unsigned)(kScTabEntries - 1))));
     *sn = __builtin_fma(Ti.x, cd, Ti.y * sd);
     *cs = __builtin_fma(Ti.y, cd, -(Ti.x * sd));
 }
+LT_DEV void sincos_turn_raw(unsigned k, const double* T, double* sn, double* cs) { sincos_turn_raw(k, sincos_turn_cell(k, T), sn, cs); }
 template <typename R> struct Mx;
 template <> struct Mx<double> {
     static LT_DEV double log(double x) { return ::log(x); }
@@ -946,6 +961,13 @@ template <typename R> LT_DEV R hg_sample_walk(R xi, const MedD<R>* M)
     const R t = Mx<R>::quot(M->one_m_g2, M->two_g * xi + M->one_m_g);
     return (M->one_p_g2 - t * t) * M->inv_2g;
 }
+// ... and from the slab walk's layer record (LayD: the same bits; two_g = 2 g is 0 exactly when g is)
+template <typename R> LT_DEV R hg_sample_walk(R xi, R two_g, R one_m_g, R one_m_g2, R one_p_g2, R inv_2g)
+{
+    if (two_g == 0) return (R)2 * xi - (R)1;
+    const R t = Mx<R>::quot(one_m_g2, two_g * xi + one_m_g);
+    return (one_p_g2 - t * t) * inv_2g;
+}
 
 // create_orthonormal_system, S/utils.py:72-80
 template <typename R> LT_DEV void onb(const R* n, R* v2, R* v3)
@@ -1079,10 +1101,9 @@ template <typename R> LT_DEV R boundary_planar(R uz, R n1, R n2, R Nr, R* cos_t_
 }
 
 // Spin (App. C.6): MCML direction update, |uz| > 0.99999 special case.
-template <typename R, bool TABLE> LT_DEV void spin(R* u, R ct, typename HeldU<R, TABLE>::type xi_phi, const double* T)      // xi_phi: the azimuth's uniform as the walk carries it (f64 XORWOW: the raw draw); T: kWalkMathTab or its LDS copy
+template <typename R> LT_DEV void spin_turn(R* u, R ct, R sp, R cp)      // sp, cp: sin / cos of the azimuth
 {
     const R st2 = Mx<R>::max0((R)1 - ct * ct);          // sin^2(theta); a rounding-negative value is 0
-    R sp, cp; HeldU<R, TABLE>::sincos_turn(xi_phi, T, &sp, &cp);
     R ux = u[0], uy = u[1], uz = u[2];
     if (Mx<R>::abs(uz) > (R)0.99999) {
         const R st = Mx<R>::sqrt_unit(st2);
@@ -1100,6 +1121,11 @@ template <typename R, bool TABLE> LT_DEV void spin(R* u, R ct, typename HeldU<R,
         u[1] = uy * k + ux * ss;
         u[2] = uz * ct - sc * t2;
     }
+}
+template <typename R, bool TABLE> LT_DEV void spin(R* u, R ct, typename HeldU<R, TABLE>::type xi_phi, const double* T)      // xi_phi: the azimuth's uniform as the walk carries it (f64 XORWOW: the raw draw); T: kWalkMathTab or its LDS copy
+{
+    R sp, cp; HeldU<R, TABLE>::sincos_turn(xi_phi, T, &sp, &cp);
+    spin_turn(u, ct, sp, cp);
 }
 
 // ---------------------------------------------------------------------------
@@ -1160,7 +1186,7 @@ template <int TALLY> LT_DEV void tally_add(void* grid, unsigned idx, typename Ta
 LT_DEV size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 template <typename R> struct LdsLayout {
-    size_t off_cnt, off_frame, off_media, off_zb, off_if, off_lm, off_tris, off_nodes, off_links, off_hist, off_march, off_math, total;
+    size_t off_cnt, off_frame, off_media, off_zb, off_if, off_lm, off_lay, off_tris, off_nodes, off_links, off_hist, off_march, off_math, total;
     __host__ __device__ LdsLayout(int n_media, int n_layers, int n_tris, int n_nodes, unsigned n_hist = 0, size_t march_bytes = 0)
     {
         auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
@@ -1171,6 +1197,7 @@ template <typename R> struct LdsLayout {
         off_zb = o;    o = al(o + (size_t)(n_layers + 1) * sizeof(R));
         off_if = o;    o = al(o + (size_t)(n_layers > 0 ? n_layers + 1 : 0) * sizeof(IfD<R>));
         off_lm = o;    o = al(o + (size_t)(n_layers > 0 ? n_layers : 1) * sizeof(int32_t));
+        off_lay = o;   o = al(o + (size_t)(n_layers > 0 ? n_layers : 0) * sizeof(LayD<R>));      // slab walks: the per-layer step records
         off_tris = o;  o = al(o + (size_t)n_tris * sizeof(TriD<R>));
         off_nodes = o; o = al(o + (size_t)n_nodes * sizeof(NodeD<R>));
         off_links = o; o = al(o + (size_t)n_nodes * 16 * sizeof(int16_t));      // front-to-back link tables (8 patterns x first | after)

@@ -16,6 +16,29 @@
 // the record of medium i in LDS by a 24-bit multiply (v_mul_u32_u24, full rate; plain indexing compiles to the quarter-rate v_mul_lo_u32)
 #ifndef LT_MED
 #define LT_MED(i) reinterpret_cast<const MedD<R>*>(reinterpret_cast<const unsigned char*>(s_med) + __umul24((unsigned)(i), (unsigned)sizeof(MedD<R>)))
+#define LT_LAY(i) reinterpret_cast<const LayD<R>*>(reinterpret_cast<const unsigned char*>(s_lay) + __umul24((unsigned)(i), (unsigned)sizeof(LayD<R>)))
+#endif
+// measurement builds of the slab walk (see its step): 1 = read the layer record's interaction fields / the math-table cells
+// where they are used instead of at the top of the step (profiles/r05a_layer_record_ab.log: both early reads pay)
+#ifndef LT_LAY_LATE
+#define LT_LAY_LATE 0
+#endif
+#ifndef LT_TAB_LATE
+#define LT_TAB_LATE 0
+#endif
+// what the interaction block (the same text for every kernel) takes from the medium: the slab kernel holds the fields of its
+// layer record (LayD, read at the top of the step), the mesh kernels read their medium's record (MedD) where they use it
+#if LT_WALK_BATCH == 0
+#define LT_STEP_Y(held, field) (kLayEarly ? held : Yp->field)
+#define LT_STEP_ABSORB LT_STEP_Y(absorb, absorb)
+#define LT_STEP_DEP LT_STEP_Y(dep, dep)
+#define LT_STEP_HG(xi) hg_sample_walk(xi, LT_STEP_Y(hg_2g, two_g), LT_STEP_Y(hg_1mg, one_m_g), LT_STEP_Y(hg_1mg2, one_m_g2), LT_STEP_Y(hg_1pg2, one_p_g2), LT_STEP_Y(hg_i2g, inv_2g))
+#define LT_STEP_G (LT_MED(s_lm[cur])->g)      // (vertex capture only: the phase function's density)
+#else
+#define LT_STEP_ABSORB Mp->absorb
+#define LT_STEP_DEP Mp->dep
+#define LT_STEP_HG(xi) hg_sample_walk(xi, Mp)
+#define LT_STEP_G (Mp->g)
 #endif
 #if LT_WALK_BATCH != 2
 template <typename R, int GEOM, bool TABLE, int TALLY, bool CAPTURE, int PHASE = 0>
@@ -47,6 +70,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
     const MedD<R>* s_med = reinterpret_cast<const MedD<R>*>(lds_raw + L.off_media);
     const R* s_zb = reinterpret_cast<const R*>(lds_raw + L.off_zb);
     const int32_t* s_lm = reinterpret_cast<const int32_t*>(lds_raw + L.off_lm);
+    [[maybe_unused]] const LayD<R>* s_lay = reinterpret_cast<const LayD<R>*>(lds_raw + L.off_lay);      // slab walks: the per-layer step records
     const IfD<R>* s_if = reinterpret_cast<const IfD<R>*>(lds_raw + L.off_if);
     const TriD<R>* s_tris = GEOM == 2 ? reinterpret_cast<const TriD<R>*>(P.tris)
                                       : reinterpret_cast<const TriD<R>*>(lds_raw + L.off_tris);
@@ -79,6 +103,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
         lds_copy(lds_raw + L.off_zb, P.zb, (size_t)(P.n_layers + 1) * sizeof(R));
         lds_copy(lds_raw + L.off_lm, P.layer_medium, (size_t)P.n_layers * sizeof(int32_t));
         lds_copy(lds_raw + L.off_if, P.ifaces, (size_t)(P.n_layers + 1) * sizeof(IfD<R>));
+        lds_copy(lds_raw + L.off_lay, P.layers, (size_t)P.n_layers * sizeof(LayD<R>));
     } else if constexpr (GEOM == 1) {
         lds_copy(lds_raw + L.off_tris, P.tris, (size_t)P.n_tris * sizeof(TriD<R>));
         lds_copy(lds_raw + L.off_nodes, P.nodes, (size_t)P.n_nodes * sizeof(NodeD<R>));
@@ -633,16 +658,38 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                     x3 = HeldU<R, TABLE>::draw(&rng);      // the fourth stays a raw draw until a boundary decision or the roulette asks for it
                 }
                 grp++;
-                const MedD<R>* Mp = LT_MED(MESH ? cur : s_lm[cur]);
-                const R mu_t = Mp->mu_t;
-                if (sleft == 0) sleft = HeldU<R, TABLE>::neg_log(x0, s_math);
-                const R s = (mu_t > 0) ? sleft * Mp->inv_mu_t : inf;
+                // Slab walks: everything the step reads about its layer is ONE record (LayD) whose address follows from `cur`
+                // alone, and the cells of the two math tables follow from the draws alone, so all of these reads are issued HERE, at
+                // the top of the step, and each is waited for where its value is first used.  The empty asm is a compiler barrier
+                // without operands: no read moves below it (left alone, each read sinks into the block that uses it and is waited for
+                // on the next line), and since it names no register nothing is waited for at it.  Two builds read the interaction's
+                // fields and the table cells where they use them, for want of registers to hold them in: the tail kernel (PHASE 2),
+                // which runs beside the log reduction in the registers that leaves, and the vertex capture.
+                // LT_LAY_LATE / LT_TAB_LATE: measurement builds without the early record / table reads.
+                static_assert(!MESH, "walk_kernel is the slab walk");
+                constexpr bool kLayEarly = PHASE != 2 && !CAPTURE && !LT_LAY_LATE;
+                constexpr bool kTabEarly = !TABLE && sizeof(R) == 8 && PHASE != 2 && !CAPTURE && !LT_TAB_LATE;
+                [[maybe_unused]] const MedD<R>* Mp = s_med;      // (the mesh branches of the shared text below; never built into this kernel)
+                const LayD<R>* Yp = LT_LAY(cur);
+                const R mu_t = Yp->mu_t, inv_mu_t = Yp->inv_mu_t, z_lo = Yp->z_lo, z_hi = Yp->z_hi;
+                [[maybe_unused]] R absorb = 0, dep = 0, hg_2g = 0, hg_1mg = 0, hg_1mg2 = 0, hg_1pg2 = 0, hg_i2g = 0;
+                [[maybe_unused]] double2 Tln, Tsc;
+                if constexpr (kTabEarly) { Tln = neg_log_cell(x0, s_math); Tsc = sincos_turn_cell(x2, s_math); }
+                if constexpr (kLayEarly) {
+                    absorb = Yp->absorb; dep = Yp->dep;
+                    hg_2g = Yp->two_g; hg_1mg = Yp->one_m_g; hg_1mg2 = Yp->one_m_g2; hg_1pg2 = Yp->one_p_g2; hg_i2g = Yp->inv_2g;
+                }
+                if constexpr (kLayEarly || kTabEarly) asm volatile("" ::: "memory");
+                if (sleft == 0) {
+                    if constexpr (kTabEarly) sleft = neg_log_raw(x0, Tln); else sleft = HeldU<R, TABLE>::neg_log(x0, s_math);
+                }
+                const R s = (mu_t > 0) ? sleft * inv_mu_t : inf;
 
                 // ---- hop: distance to the next boundary ----
                 R tb = inf; int hit_tri = -1;
                 if constexpr (!MESH) {
                     if (uz != 0) {
-                        const R dz = (uz > 0 ? s_zb[cur + 1] : s_zb[cur]) - pz;   // sign of uz, or 0
+                        const R dz = (uz > 0 ? z_hi : z_lo) - pz;   // the layer's own bounds, from its record: sign of uz, or 0
                         // A hop that ends well inside the layer needs no quotient: |dz| > s |uz| (1 + d) with
                         // d >= 8 ulp implies fl(dz / uz) > s, so `tb <= s` below is false either way and tb is
                         // not read.  Only lanes within a step of an interface pay for the IEEE division.
@@ -727,12 +774,12 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                     // ---- interaction site: move, drop, spin, roulette ----
                     px += ux * s; py += uy * s; pz += uz * s;
                     sleft = 0;
-                    const R dw = w * Mp->absorb;
+                    const R dw = w * LT_STEP_ABSORB;
                     if constexpr (CAPTURE) if (P.vertices) {    // pdf_dir = the reference's henyey_greenstein at the deflection the spin below samples (its sign
                                          // convention: -cos); recomputed here so that the capture costs the plain walk no register
-                        const R ct_c = hg_sample_walk(u1, Mp);
+                        const R ct_c = LT_STEP_HG(u1);
                         record_vertex<R>(P, pid - P.photon_offset, nv, px, py, pz, ux, uy, uz, w, LT_VERTEX_VOLUME, cur, step, (R)0, (R)0, (R)0,
-                                         (R)0, (w - dw > 0) ? hg_pdf(-ct_c, Mp->g) : (R)0);
+                                         (R)0, (w - dw > 0) ? hg_pdf(-ct_c, LT_STEP_G) : (R)0);
                     }
                     const R fx = (px - gx0) * ivx, fy = (py - gy0) * ivy, fz = (pz - gz0) * ivz;
                     // branch-free: nearly every deposit is inside the grid, so the index is computed for all lanes
@@ -751,7 +798,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                         ? (((__umul24(__umul24(vz >> kTileBZ, P.log_nty) + (vy >> kTileBY), P.log_ntx) + (vx >> kTileBX)) << kTileShift)      // (<= 65536 tiles: 24-bit products, full rate)
                            | ((vz & 15u) << 10) | ((vy & 31u) << 5) | (vx & 31u))
                         : (vz * (unsigned)P.ny + vy) * (unsigned)P.nx + vx;
-                    const TV q = tally_quantum<TALLY, R>(w * Mp->dep);     // the tally quantity: absorbed weight, or w / mu_t (fluence)
+                    const TV q = tally_quantum<TALLY, R>(w * LT_STEP_DEP);     // the tally quantity: absorbed weight, or w / mu_t (fluence)
                     const bool same = inside && idx == pend_idx;
                     const bool flush = inside && !same;
                     f_idx = flush ? pend_idx : kNoVoxel; f_val = pend_val;
@@ -763,7 +810,13 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                     if (!(w > 0)) alive = false;
                     else {
                         R u[3] = {ux, uy, uz};
-                        spin<R, TABLE>(u, hg_sample_walk(u1, Mp), x2, s_math);
+#if LT_WALK_BATCH == 0
+                        if constexpr (kTabEarly) {
+                            R sp, cp; sincos_turn_raw(x2, Tsc, &sp, &cp);
+                            spin_turn(u, LT_STEP_HG(u1), sp, cp);
+                        } else
+#endif
+                        spin<R, TABLE>(u, LT_STEP_HG(u1), x2, s_math);
                         ux = u[0]; uy = u[1]; uz = u[2];
                         if (w < (R)1e-4) {  // weight roulette; shape of S/path_tracing_fix1.py:126-132
                             if (HeldU<R, TABLE>::get(x3) <= (R)0.1) { atomicAdd(&s_cnt[CW_ROULETTE], -9.0 * (double)w); w *= (R)10; }
@@ -830,6 +883,13 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
         __hip_atomic_fetch_add(&P.counters->w[threadIdx.x], s_cnt[threadIdx.x], __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
 }
+#undef LT_STEP_ABSORB
+#if LT_WALK_BATCH == 0
+#undef LT_STEP_Y
+#endif
+#undef LT_STEP_DEP
+#undef LT_STEP_HG
+#undef LT_STEP_G
 #if LT_INV_MODE == 2
 #undef gx0
 #undef gy0
