@@ -264,7 +264,47 @@ int lt_last_log_hot_tiles(lt_ctx* ctx, uint32_t* hot_tiles, uint32_t* threshold)
 int lt_read_grid(lt_ctx* ctx, void* host_out, size_t bytes);
 /* blocking D2H, converted to float64 absorbed weight per voxel */
 int lt_read_grid_f64(lt_ctx* ctx, double* host_out, size_t n_voxels);
+/* the inverse of lt_read_grid: blocking H2D of a raw tally ([nz][ny][nx], dtype as set, bytes = the grid's size) on the ctx
+ * stream.  Overwrites the grid and leaves the counters as they are: restores a saved tally so that further launches
+ * accumulate onto it.  LT_E_STATE without a grid, LT_E_INVALID on a size mismatch. */
+int lt_write_grid(lt_ctx* ctx, const void* host_in, size_t bytes);
 int lt_read_counters(lt_ctx* ctx, lt_counters* out);
+
+/* ---- sums of the tally, taken on the device ------------------------------ */
+/* What most users want from a run is far smaller than the grid: absorbed weight against depth, a projection, the
+ * cylindrical map A(r, z).  The two calls below read the grid once in HBM and return a few KiB; both run on the ctx stream
+ * (ordered behind earlier launches, as lt_read_grid is) and block until the output is filled.  Device memory beyond the
+ * grid: partial sums and the output, in the ctx's scratch buffers.
+ *   out      (required) f64 weight per bin, in the units of lt_read_grid_f64
+ *   raw_out  (may be NULL; non-NULL only with LT_TALLY_U64FX, else LT_E_INVALID) the exact integer sums
+ * LT_TALLY_U64FX: summed in integers, out = (double)raw * 2^-40 -- independent of the order, bit-reproducible.  The integer
+ * sums wrap modulo 2^64: ONE BIN holds at most 2^24 = 1.68e7 units of weight, the bound stated above for a voxel.
+ * LT_TALLY_F32 / LT_TALLY_F64: every voxel is widened to f64 and summed in f64.
+ * LT_E_STATE without a grid. */
+
+/* Sum the grid over the axes that are NOT kept.  keep_mask bits: 1 = x, 2 = y, 4 = z.  out is C-order over the kept axes in
+ * z, y, x order: 4 -> [nz] (the depth profile), 3 -> [ny][nx], 5 -> [nz][nx], 6 -> [nz][ny], 1 -> [nx], 2 -> [ny], 0 -> one
+ * number, the grid total.  7 (that is lt_read_grid) or any other bit: LT_E_INVALID.
+ * Float tallies too are summed in a FIXED ORDER (partial sums, then a finishing pass; the order depends on the grid's shape
+ * alone): two calls on an unchanged grid return identical bits. */
+int lt_tally_sum_axes(lt_ctx* ctx, int keep_mask, double* out, uint64_t* raw_out);
+/* Per z, sum the (y, x) columns bin by bin.  bin_of_column: host array [ny][nx], a bin in 0 .. n_bins-1 per column or -1 to
+ * leave the column out (any other value: LT_E_INVALID).  out [nz][n_bins]: for every z the sum of the voxels whose column
+ * carries that bin; a bin with no column is 0.  1 <= n_bins <= 4096; more: LT_E_UNSUPPORTED.  With a table of
+ * lt_radial_bins this is the r-z map; with a 0 / -1 mask, any region of interest.
+ * Float tallies are added into per-workgroup bins with LDS atomics: the result may differ from call to call in the last bits
+ * (by the usual bound for a sum of n non-negative terms, n 2^-53 relative); the u64 fixed-point result is exact. */
+int lt_tally_sum_columns(lt_ctx* ctx, const int32_t* bin_of_column, int n_bins, double* out, uint64_t* raw_out);
+/* The table of lt_tally_sum_columns for rings about an axis parallel to z.  Pure host code: no ctx, no device.  For the
+ * column (iy, ix) of an nx x ny grid, each line ONE IEEE double operation per operator (a NumPy restatement gives the same
+ * integers):
+ *     xc = origin_x + (ix + 0.5) * voxel_x          dx = xc - centre_x          (likewise yc, dy)
+ *     r = sqrt(dx * dx + dy * dy)                    bin = (int)floor(r / dr),   any bin >= nr becomes nr
+ * bins_out [ny][nx] holds 0 .. nr: nr + 1 bins, the last collecting everything beyond nr * dr, so that the map's total is the
+ * grid's.  dr <= 0, nr < 1 or non-positive dimensions: LT_E_INVALID. */
+int lt_radial_bins(int nx, int ny, const double origin_xy[2], const double voxel_xy[2], const double centre_xy[2], double dr,
+                   int nr, int32_t* bins_out);
+
 int lt_grid_device_ptr(lt_ctx* ctx, void** ptr, size_t* bytes);
 int lt_counters_device_ptr(lt_ctx* ctx, void** ptr, size_t* bytes);
 void* lt_stream(lt_ctx* ctx); /* hipStream_t of the ctx */

@@ -30,7 +30,7 @@ SYMBOLS = [
     "lt_set_surface_materials", "lt_set_lights", "lt_render_surface", "lt_set_vertex_capture", "lt_read_vertices",
     "lt_set_tally_mode", "lt_last_log_stages", "lt_reserve_log", "lt_render_surface_old", "lt_set_overlap", "lt_last_log_hot_tiles",
     "lt_last_log_info", "lt_set_tally_quantity", "lt_set_tuning", "lt_mesh_accel_info", "lt_build_bvh",
-    "lt_layer_records",
+    "lt_layer_records", "lt_tally_sum_axes", "lt_tally_sum_columns", "lt_radial_bins", "lt_write_grid",
 ]
 
 # lt_vertex as a NumPy record (112 bytes, same layout as the C struct)
@@ -75,6 +75,44 @@ def layer_records(media, z_bounds, medium_idx, quantity=0, f32=False):
     if rc:
         raise LtError("lt_layer_records failed (%d): needs len(z_bounds) == len(medium_idx) + 1 and medium indices inside the media" % rc)
     return m_out, z_out, r_out
+
+
+_KEEP_BITS = {"x": 1, "y": 2, "z": 4}
+
+
+def keep_mask(keep):
+    """The keep_mask of lt_tally_sum_axes from a string of the kept axes out of "xyz" in any order ("" keeps none: the grid
+    total) or from the mask itself (0..6); all three axes kept is the grid: read_grid."""
+    if isinstance(keep, str):
+        k = keep.lower()
+        if any(ch not in _KEEP_BITS for ch in k) or len(set(k)) != len(k):
+            raise ValueError("keep=%r: a string of distinct axes out of 'x', 'y', 'z'" % (keep,))
+        m = sum(_KEEP_BITS[ch] for ch in k)
+    elif isinstance(keep, (int, np.integer)) and not isinstance(keep, bool):
+        m = int(keep)
+    else:
+        raise ValueError("keep=%r: a string of axes or a mask 0..6" % (keep,))
+    if not 0 <= m <= 6:
+        raise ValueError("keep=%r: at least one axis has to be summed (mask 0..6); the whole grid is read_grid()" % (keep,))
+    return m
+
+
+def kept_shape(mask, grid_shape):
+    """Shape of tally_sum's result: the kept axes of grid_shape = (nz, ny, nx), in that order."""
+    return tuple(n for n, bit in zip(grid_shape, (4, 2, 1)) if mask & bit)
+
+
+def radial_bins(shape_xy, origin_xy, voxel_xy, centre_xy, dr, nr):
+    """lt_radial_bins (host C++, no device): int32 [ny, nx], the ring 0..nr-1 of width dr about centre_xy that every column's
+    centre falls in, nr for everything beyond nr * dr -- the table Context.tally_sum_columns(bins, nr + 1) takes."""
+    nx, ny = (int(v) for v in shape_xy)
+    out = np.empty((max(ny, 0), max(nx, 0)), dtype=np.int32)
+    pair = lambda v: (C.c_double * 2)(*[float(x) for x in v][:2])      # noqa: E731
+    rc = lib().lt_radial_bins(C.c_int(nx), C.c_int(ny), pair(origin_xy), pair(voxel_xy), pair(centre_xy), C.c_double(float(dr)),
+                              C.c_int(int(nr)), _ip(out))
+    if rc:
+        raise LtError("lt_radial_bins failed (%d): needs nx, ny >= 1, dr > 0 and nr >= 1" % rc)
+    return out
 
 
 class Medium(C.Structure):
@@ -368,6 +406,41 @@ class Context:
         out = np.empty(self._grid_shape, dtype=np.float64)
         self._ck(lib().lt_read_grid_f64(self._h, _dp(out), C.c_size_t(out.size)), "lt_read_grid_f64")
         return out
+
+    def write_grid(self, array):
+        """Overwrite the device grid with a raw tally [nz, ny, nx] of the dtype the grid was set with (what read_grid_raw
+        returned); the counters stay as they are."""
+        a = np.asarray(array)
+        if self._grid_shape is not None and (a.dtype != np.dtype(TALLY_NP[self._tally]) or a.shape != self._grid_shape):
+            raise LtError("write_grid: expected %s %s, got %s %s" % (np.dtype(TALLY_NP[self._tally]).name, self._grid_shape,
+                                                                     a.dtype.name, a.shape))
+        a = np.ascontiguousarray(a)
+        self._ck(lib().lt_write_grid(self._h, a.ctypes.data_as(C.c_void_p), C.c_size_t(a.nbytes)), "lt_write_grid")
+
+    def _sum_buffers(self, shape, raw):
+        out = np.empty(shape, dtype=np.float64)
+        rawbuf = np.empty(shape, dtype=np.uint64) if raw else None
+        return out, rawbuf, (rawbuf.ctypes.data_as(C.POINTER(C.c_uint64)) if raw else None)
+
+    def tally_sum(self, keep, raw=False):
+        """The grid summed on the device over the axes not in ``keep`` ("", "x", "y", "z", "xy", "xz", "yz" in any letter
+        order, or the mask: 1 = x, 2 = y, 4 = z): float64 weight shaped by the kept axes in (z, y, x) order -- "z" is the
+        depth profile [nz], "" the grid total (0-d).  raw=True (u64 fixed-point tally only): the exact uint64 sums."""
+        m = keep_mask(keep)
+        out, rawbuf, rp = self._sum_buffers(kept_shape(m, self._grid_shape or (0, 0, 0)), raw)
+        self._ck(lib().lt_tally_sum_axes(self._h, C.c_int(m), _dp(out), rp), "lt_tally_sum_axes")
+        return rawbuf if raw else out
+
+    def tally_sum_columns(self, bins, n_bins, raw=False):
+        """[nz, n_bins]: for every z the sum of the voxels whose (y, x) column carries that bin.  ``bins``: int [ny, nx],
+        0..n_bins-1 or -1 to leave a column out (radial_bins gives the table of an r-z map).  raw as in tally_sum."""
+        b = np.ascontiguousarray(bins, dtype=np.int32)
+        nz, ny, nx = self._grid_shape or (0, 0, 0)
+        if self._grid_shape is not None and b.shape != (ny, nx):
+            raise LtError("tally_sum_columns: bins must have shape (ny, nx) = %s, got %s" % ((ny, nx), b.shape))
+        out, rawbuf, rp = self._sum_buffers((nz, max(int(n_bins), 0)), raw)
+        self._ck(lib().lt_tally_sum_columns(self._h, _ip(b), C.c_int(int(n_bins)), _dp(out), rp), "lt_tally_sum_columns")
+        return rawbuf if raw else out
 
     def read_counters(self):
         c = Counters()

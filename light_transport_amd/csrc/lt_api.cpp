@@ -1572,6 +1572,18 @@ int lt_read_grid_f64(lt_ctx* c, double* host_out, size_t n_voxels)
     return LT_OK;
 }
 
+int lt_write_grid(lt_ctx* c, const void* host_in, size_t bytes)
+{
+    CHECK_CTX(c);
+    if (!c->have_grid) return c->fail(LT_E_STATE, "lt_write_grid: no grid");
+    if (!host_in || bytes != c->n_vox() * c->grid_elem())
+        return c->fail(LT_E_INVALID, "lt_write_grid: expected %zu bytes", c->n_vox() * c->grid_elem());
+    BIND(c);
+    HIP_TRY(c, hipMemcpyAsync(c->d_grid.p, host_in, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return LT_OK;
+}
+
 int lt_read_counters(lt_ctx* c, lt_counters* out)
 {
     CHECK_CTX(c);
@@ -1667,6 +1679,88 @@ int stage_in(lt_ctx* c, DevBuf& b, const void* h, size_t bytes)
     return LT_OK;
 }
 }  // namespace
+
+// ---- sums of the tally on the device (kernels: lt_tallysum.hip) -----------
+namespace {
+// what both sums share: the checks of the outputs, and the way back -- n_out doubles at the start of d_scratch_out, the
+// integer sums (u64 fixed point only) behind them
+int sum_outputs_ok(lt_ctx* c, const char* who, const double* out, const uint64_t* raw_out)
+{
+    if (!c->have_grid) return c->fail(LT_E_STATE, "%s: no grid", who);
+    if (!out) return c->fail(LT_E_INVALID, "%s: out is required", who);
+    if (raw_out && c->tally != LT_TALLY_U64FX) return c->fail(LT_E_INVALID, "%s: raw_out needs the LT_TALLY_U64FX tally", who);
+    return LT_OK;
+}
+int sum_read_back(lt_ctx* c, size_t n_out, double* out, uint64_t* raw_out)
+{
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch_out.p, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    if (raw_out) HIP_TRY(c, hipMemcpyAsync(raw_out, (char*)c->d_scratch_out.p + n_out * 8, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return LT_OK;
+}
+}  // namespace
+
+int lt_tally_sum_axes(lt_ctx* c, int keep_mask, double* out, uint64_t* raw_out)
+{
+    CHECK_CTX(c);
+    int rc = sum_outputs_ok(c, "lt_tally_sum_axes", out, raw_out);
+    if (rc) return rc;
+    if (keep_mask < 0 || keep_mask > 6)
+        return c->fail(LT_E_INVALID, "lt_tally_sum_axes: keep_mask %d (bits 1 = x, 2 = y, 4 = z; all three kept is lt_read_grid)", keep_mask);
+    BIND(c);
+    size_t partial_bytes = 0;
+    const size_t n_out = tally_sum_axes_plan(c->nx, c->ny, c->nz, keep_mask, c->tally, &partial_bytes);
+    HIP_TRY(c, c->d_scratch_in.ensure(partial_bytes));
+    HIP_TRY(c, c->d_scratch_out.ensure(n_out * 16));
+    double* d_out = (double*)c->d_scratch_out.p;
+    HIP_TRY(c, launch_tally_sum_axes(c->d_grid.p, c->tally, c->nx, c->ny, c->nz, keep_mask, c->d_scratch_in.p, d_out,
+                                     c->tally == LT_TALLY_U64FX ? (unsigned long long*)(d_out + n_out) : nullptr, c->stream));
+    return sum_read_back(c, n_out, out, raw_out);
+}
+
+int lt_tally_sum_columns(lt_ctx* c, const int32_t* bin_of_column, int n_bins, double* out, uint64_t* raw_out)
+{
+    CHECK_CTX(c);
+    int rc = sum_outputs_ok(c, "lt_tally_sum_columns", out, raw_out);
+    if (rc) return rc;
+    if (!bin_of_column || n_bins < 1) return c->fail(LT_E_INVALID, "lt_tally_sum_columns: need a table and n_bins >= 1");
+    if (n_bins > kMaxSumBins)
+        return c->fail(LT_E_UNSUPPORTED, "lt_tally_sum_columns: %d bins, at most %d (the bins of a plane are summed in LDS)", n_bins, kMaxSumBins);
+    const size_t n_cols = (size_t)c->nx * (size_t)c->ny;
+    for (size_t i = 0; i < n_cols; i++)
+        if (bin_of_column[i] < -1 || bin_of_column[i] >= n_bins)
+            return c->fail(LT_E_INVALID, "lt_tally_sum_columns: column %zu has bin %d, outside -1 .. %d", i, bin_of_column[i], n_bins - 1);
+    BIND(c);
+    const size_t n_out = (size_t)c->nz * (size_t)n_bins;
+    HIP_TRY(c, c->d_scratch_aux.ensure(tally_sum_columns_plan(c->nx, c->ny, c->nz, n_bins)));
+    HIP_TRY(c, c->d_scratch_out.ensure(n_out * 16));
+    rc = stage_in(c, c->d_scratch_in, bin_of_column, n_cols * sizeof(int32_t));
+    if (rc) return rc;
+    double* d_out = (double*)c->d_scratch_out.p;
+    HIP_TRY(c, launch_tally_sum_columns(c->d_grid.p, c->tally, c->nx, c->ny, c->nz, (const int32_t*)c->d_scratch_in.p, n_bins,
+                                        c->d_scratch_aux.p, d_out, c->tally == LT_TALLY_U64FX ? (unsigned long long*)(d_out + n_out) : nullptr,
+                                        c->stream));
+    // the copy of the table has left the caller's array when this returns: sum_read_back waits for the stream
+    return sum_read_back(c, n_out, out, raw_out);
+}
+
+int lt_radial_bins(int nx, int ny, const double origin_xy[2], const double voxel_xy[2], const double centre_xy[2], double dr, int nr,
+                   int32_t* bins_out)
+{
+    if (nx <= 0 || ny <= 0 || !origin_xy || !voxel_xy || !centre_xy || !bins_out || !(dr > 0) || nr < 1) return LT_E_INVALID;
+    for (int iy = 0; iy < ny; iy++) {
+        const double yc = origin_xy[1] + (iy + 0.5) * voxel_xy[1];
+        const double dy = yc - centre_xy[1];
+        for (int ix = 0; ix < nx; ix++) {
+            const double xc = origin_xy[0] + (ix + 0.5) * voxel_xy[0];
+            const double dx = xc - centre_xy[0];
+            const double r = std::sqrt(dx * dx + dy * dy);
+            const double b = std::floor(r / dr);
+            bins_out[(size_t)iy * nx + ix] = !(b < (double)nr) ? nr : (int32_t)b;      // (not-a-number too: the overflow bin)
+        }
+    }
+    return LT_OK;
+}
 
 // the front-to-back link tables of the ctx mesh on the device (upload_tables has put them there with the mesh), or null
 // when the mesh has none (a BVH beyond 32767 nodes: the links are 16-bit) -- d_links may still hold an earlier mesh's

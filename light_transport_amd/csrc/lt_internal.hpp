@@ -328,4 +328,16 @@ hipError_t launch_rng_raw(unsigned long long seed, unsigned long long photon_id,
 hipError_t launch_grid_to_f64(const void* grid, int tally, size_t n, double* out, hipStream_t s);
 hipError_t launch_grid_add(void* dst, const void* src, int tally, size_t n, hipStream_t s);   // dst += src
 
+// Sums of the voxel tally on the device (lt_tallysum.hip).  The *_plan functions (host only) say what a call needs: the sums
+// go through partial sums in a scratch buffer of `partial_bytes`; out gets n_out doubles, raw (null unless the tally is u64
+// fixed point) the integer sums.  keep_mask 0..6 (bit 0 x, 1 y, 2 z); bins: device copy of the [ny][nx] table, every entry
+// checked by the caller to lie in -1 .. n_bins - 1 (the kernel indexes LDS with it).
+size_t tally_sum_axes_plan(int nx, int ny, int nz, int keep_mask, int tally, size_t* partial_bytes);   // returns n_out
+hipError_t launch_tally_sum_axes(const void* grid, int tally, int nx, int ny, int nz, int keep_mask, void* partials, double* out,
+                                 unsigned long long* raw, hipStream_t s);
+constexpr int kMaxSumBins = 4096;    // the bins of a column sum live in LDS, 8 bytes each
+size_t tally_sum_columns_plan(int nx, int ny, int nz, int n_bins);   // returns partial_bytes; n_out = nz * n_bins
+hipError_t launch_tally_sum_columns(const void* grid, int tally, int nx, int ny, int nz, const int32_t* bins, int n_bins, void* partials,
+                                    double* out, unsigned long long* raw, hipStream_t s);
+
 }  // namespace ltk

@@ -95,3 +95,22 @@ def reduce_host(grid, counters, group=None, dst=None):
     c = {k: int(v) for k, v in zip(keys_i, ci.tolist())}
     c.update({k: float(v) for k, v in zip(keys_f, cf.tolist())})
     return out.reshape(grid.shape), c
+
+
+def reduce_sums_host(arrays, group=None, dst=None):
+    """Sum-reduce a list of small NumPy arrays (gloo) -- the profiles and maps of Context.tally_sum / tally_sum_columns, so that
+    ranks combine a few KiB each instead of their grids.  uint64 (the raw sums of the fixed-point tally) travels as int64: same
+    bits, same sum modulo 2^64, so the reduced raw profile equals the single-process one bit for bit.  dst=None: all-reduce.
+    Returns new arrays of the same shapes and dtypes (the sums on ``dst``, or everywhere)."""
+    out = []
+    for a in arrays:
+        a = np.array(a, copy=True, order="C")
+        if a.dtype not in (np.uint64, np.int64, np.float64, np.float32):
+            raise TypeError("reduce_sums_host: uint64, int64, float64 or float32 arrays, not %s" % a.dtype)
+        t = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a)
+        if dst is None:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        else:
+            dist.reduce(t, dst=dst, op=dist.ReduceOp.SUM, group=group)
+        out.append(a)
+    return out

@@ -170,6 +170,44 @@ class PhotonTracer:
             raise ValueError("fluence(): nothing traced since the last reset")
         return self.ctx.read_grid() / (self.grid.voxel_volume * float(self.photons))
 
+    # -- sums taken on the device: a few KiB come back instead of the grid ------------------------------------------
+    def _normalised(self, weight, voxels):
+        """quantity="absorbed": the summed weight; "fluence": the mean fluence over the ``voxels`` (a count, or an array of
+        counts) that went into each bin -- sum / (voxels x voxel volume x photons), NaN for a bin without voxels."""
+        if self.quantity != "fluence":
+            return weight
+        if self.photons <= 0:
+            raise ValueError("nothing traced since the last reset")
+        n = np.asarray(voxels, dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return weight / (np.where(n > 0, n, np.nan) * (self.grid.voxel_volume * float(self.photons)))
+
+    def depth_profile(self):
+        """float64 [nz]: absorbed weight per z layer of voxels, absorbed().sum((1, 2)) -- or the mean fluence of the layer --
+        summed on the device (Context.tally_sum)."""
+        nx, ny, _ = self.grid.shape
+        return self._normalised(self.ctx.tally_sum("z"), nx * ny)
+
+    def projection(self, axis):
+        """The grid summed along one axis -- "x", "y" or "z", or the axis number of the [nz, ny, nx] array (0 = z, 1 = y,
+        2 = x), so that projection(a) is absorbed().sum(a): [ny, nx] along z, [nz, nx] along y, [nz, ny] along x.  For a
+        fluence tracer the mean fluence along the axis."""
+        name = axis if isinstance(axis, str) else {0: "z", 1: "y", 2: "x", -1: "x", -2: "y", -3: "z"}.get(axis)
+        if name not in ("x", "y", "z"):
+            raise ValueError("projection(): axis must be 'x', 'y', 'z' or 0, 1, 2 (z, y, x), not %r" % (axis,))
+        return self._normalised(self.ctx.tally_sum("xyz".replace(name, "")), self.grid.shape["xyz".index(name)])
+
+    def rz_map(self, centre_xy, dr, nr):
+        """(map [nz, nr + 1], r_edges [nr + 2]): the grid summed over rings of width ``dr`` about the axis through
+        ``centre_xy`` parallel to z.  Ring k holds the columns whose centre lies in [r_edges[k], r_edges[k + 1]); the last one,
+        [nr dr, inf), collects the rest, so the map's total is the grid's.  Absorbed weight per ring and z, or the mean
+        fluence over the ring's voxels (NaN where a ring holds no column)."""
+        nx, ny, _ = self.grid.shape
+        bins = _lib.radial_bins((nx, ny), self.grid.origin[:2], self.grid.voxel[:2], centre_xy, dr, nr)
+        m = self.ctx.tally_sum_columns(bins, int(nr) + 1)
+        edges = np.append(float(dr) * np.arange(int(nr) + 1), np.inf)
+        return self._normalised(m, np.bincount(bins.ravel(), minlength=int(nr) + 1)[None, :]), edges
+
     def absorbed_raw(self):
         return self.ctx.read_grid_raw()
 
