@@ -305,6 +305,54 @@ int lt_tally_sum_columns(lt_ctx* ctx, const int32_t* bin_of_column, int n_bins, 
 int lt_radial_bins(int nx, int ny, const double origin_xy[2], const double voxel_xy[2], const double centre_xy[2], double dr,
                    int nr, int32_t* bins_out);
 
+/* ---- statistical error of the tally, from batch moments on the device --- */
+/* How far can a voxel's number be trusted?  Trace the photons in N batches of EQUAL size and close every batch with
+ * lt_stats_fold.  With statistics on the ctx owns two more device buffers of the grid's extent: `prev`, the grid as it stood at
+ * the last fold (the tally's own type), and `m2` (f64), the sum over the closed batches of the squared batch contribution.
+ * A fold does, per voxel (m2 + d * d is one rounded multiply, then one rounded add -- no fused multiply-add):
+ *     d = grid - prev     LT_TALLY_U64FX: the integer difference, then (double)diff * 2^-40;  f32 / f64: (double)grid - (double)prev
+ *     m2 = m2 + d * d     prev = grid
+ * The estimator is that of batch means.  With S1 = prev in the units of lt_read_grid_f64, each line a single IEEE double
+ * operation (a NumPy restatement gives the same bits up to the rounding of its divide and square root):
+ *     S1 == 0 -> NaN (no estimate)       q = (N * m2) / (S1 * S1)       v = q - 1, v < 0 -> 0       R = sqrt(v / (N - 1))
+ * R is the relative standard error of the mean over the N batches: 1 where a single batch contributed, 0 where all of them
+ * contributed equally.  It means what it says only if the batches are of equal size (the same number of photons each); results
+ * do not depend on how a batch's photon ids were split into launches.  Voxels of one batch are correlated, so the error of a
+ * SUM of voxels (a depth profile) does not follow from the per-voxel moments: take lt_tally_sum_axes after every fold and keep
+ * the moments of the per-batch sums on the host.
+ * While statistics are on: lt_zero_tally also zeroes prev, m2 and N; lt_set_grid turns statistics off; lt_write_grid stays
+ * legal (the next fold books the difference as a batch); lt_reduce_grid across ranks is NOT supported (prev and m2 stay
+ * local: the moments would no longer belong to the grid).  With statistics off no other call changes in any way.
+ * Every call below: LT_E_STATE while statistics are off, LT_E_INVALID on a NULL output or a wrong n_voxels. */
+
+/* on != 0: allocate and zero prev and m2, N = 0 (again, if statistics were on already).  LT_E_STATE without a grid, or if
+ * anything was launched into or written to the grid since the last lt_set_grid / lt_zero_tally (prev is the grid only while
+ * both are zero); LT_E_NOMEM if the device cannot hold 8 + sizeof(tally element) more bytes per voxel.
+ * on == 0: release the buffers (never an error). */
+int lt_stats_enable(lt_ctx* ctx, int on);
+/* Close a batch: N += 1.  Asynchronous, on the ctx stream, ordered behind earlier launches exactly as lt_read_grid is.  A pure
+ * streaming pass: a 16-byte group whose grid and prev bits are equal writes nothing and does not read m2, so a fold of a traced
+ * grid costs about two reads of the grid.  A fold with nothing traced since the last one is a batch of zeros.  A grid that
+ * holds LESS than prev (a smaller tally was written over it) is the caller's error: the result is unspecified. */
+int lt_stats_fold(lt_ctx* ctx);
+/* N, the number of closed batches */
+int lt_stats_batches(lt_ctx* ctx, uint64_t* n_out);
+/* blocking D2H of m2, [nz][ny][nx] f64 */
+int lt_stats_read_m2(lt_ctx* ctx, double* out, size_t n_voxels);
+/* blocking: R per voxel, [nz][ny][nx] f64 (NaN where S1 == 0), through the ctx's scratch buffer as lt_read_grid_f64 goes.
+ * LT_E_STATE if N < 2. */
+int lt_stats_read_relerr(lt_ctx* ctx, double* out, size_t n_voxels);
+/* blocking: "how many voxels, holding how much of the weight, are below x % error" without reading a grid back.  edges:
+ * 1 <= n_edges <= 63 finite, non-negative, strictly ascending values (anything else LT_E_INVALID; more than 63
+ * LT_E_UNSUPPORTED).  The class of a voxel is the number of edges <= R -- the R lt_stats_read_relerr returns for it, computed
+ * by the same device function.  voxels_out, weight_out (both required) and raw_weight_out [n_edges + 2]: per class 0 .. n_edges
+ * the voxels and the sum of their S1; the last entry is the class of the voxels with S1 == 0, whose weight is 0.  The voxel
+ * counts, and with LT_TALLY_U64FX the weights, are integer sums: exact.  Float tallies are widened to f64 and added into
+ * per-workgroup bins with LDS atomics, then in a fixed order: the last bits may differ from call to call.  raw_weight_out: may
+ * be NULL; non-NULL only with LT_TALLY_U64FX (else LT_E_INVALID), the integer sums.  LT_E_STATE if N < 2. */
+int lt_stats_summary(lt_ctx* ctx, const double* edges, int n_edges, uint64_t* voxels_out, double* weight_out,
+                     uint64_t* raw_weight_out);
+
 int lt_grid_device_ptr(lt_ctx* ctx, void** ptr, size_t* bytes);
 int lt_counters_device_ptr(lt_ctx* ctx, void** ptr, size_t* bytes);
 void* lt_stream(lt_ctx* ctx); /* hipStream_t of the ctx */

@@ -31,7 +31,18 @@ SYMBOLS = [
     "lt_set_tally_mode", "lt_last_log_stages", "lt_reserve_log", "lt_render_surface_old", "lt_set_overlap", "lt_last_log_hot_tiles",
     "lt_last_log_info", "lt_set_tally_quantity", "lt_set_tuning", "lt_mesh_accel_info", "lt_build_bvh",
     "lt_layer_records", "lt_tally_sum_axes", "lt_tally_sum_columns", "lt_radial_bins", "lt_write_grid",
+    "lt_stats_enable", "lt_stats_fold", "lt_stats_batches", "lt_stats_read_m2", "lt_stats_read_relerr", "lt_stats_summary",
 ]
+_U64P = C.POINTER(C.c_uint64)
+# prototypes of the lt_stats_* entry points (lt.h); every one returns int
+PROTOTYPES = {
+    "lt_stats_enable": [C.c_void_p, C.c_int],
+    "lt_stats_fold": [C.c_void_p],
+    "lt_stats_batches": [C.c_void_p, _U64P],
+    "lt_stats_read_m2": [C.c_void_p, C.POINTER(C.c_double), C.c_size_t],
+    "lt_stats_read_relerr": [C.c_void_p, C.POINTER(C.c_double), C.c_size_t],
+    "lt_stats_summary": [C.c_void_p, C.POINTER(C.c_double), C.c_int, _U64P, C.POINTER(C.c_double), _U64P],
+}
 
 # lt_vertex as a NumPy record (112 bytes, same layout as the C struct)
 VERTEX_DTYPE = np.dtype([("point", "<f8", 3), ("direction", "<f8", 3), ("g_norm", "<f8", 3), ("throughput", "<f8"),
@@ -115,6 +126,20 @@ def radial_bins(shape_xy, origin_xy, voxel_xy, centre_xy, dr, nr):
     return out
 
 
+def relative_error(n, s1, m2):
+    """The estimator of lt.h in NumPy, every line one IEEE double operation per element: the relative standard error of the
+    mean over ``n`` equal batches from the total ``s1`` and the sum ``m2`` of the squared batch contributions.  Arrays in, an
+    array out; NaN where s1 == 0 (no estimate), 0 where rounding leaves q < 1."""
+    n = np.float64(n)
+    s1, m2 = np.asarray(s1, dtype=np.float64), np.asarray(m2, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = (n * m2) / (s1 * s1)
+        v = q - 1.0
+        v = np.where(v < 0.0, 0.0, v)
+        r = np.sqrt(v / (n - 1.0))
+    return np.where(s1 == 0.0, np.nan, r)
+
+
 class Medium(C.Structure):
     _fields_ = [("mu_a", C.c_double), ("mu_s", C.c_double), ("g", C.c_double), ("n", C.c_double)]
 
@@ -189,6 +214,10 @@ def lib():
         L.lt_last_error.argtypes = [C.c_void_p]
         L.lt_stream.restype = C.c_void_p
         L.lt_stream.argtypes = [C.c_void_p]
+        for name, argtypes in PROTOTYPES.items():
+            f = getattr(L, name, None)      # (an older build of the ABI behind LT_HIP_LIBRARY: the call then fails by name)
+            if f is not None:
+                f.argtypes, f.restype = argtypes, C.c_int
         _lib = L
     return _lib
 
@@ -441,6 +470,48 @@ class Context:
         out, rawbuf, rp = self._sum_buffers((nz, max(int(n_bins), 0)), raw)
         self._ck(lib().lt_tally_sum_columns(self._h, _ip(b), C.c_int(int(n_bins)), _dp(out), rp), "lt_tally_sum_columns")
         return rawbuf if raw else out
+
+    # -- statistical error of the tally from batch moments (lt.h: lt_stats_*) ------------------------------------------
+    def stats_enable(self, on=True):
+        """Turn the batch statistics on (two more device buffers of the grid's extent, zeroed; needs a grid nothing was
+        launched into or written to since set_grid / zero_tally) or off."""
+        self._ck(lib().lt_stats_enable(self._h, int(bool(on))), "lt_stats_enable")
+
+    def stats_fold(self):
+        """Close a batch (async): what the grid gained since the last fold goes, squared, into the second moments."""
+        self._ck(lib().lt_stats_fold(self._h), "lt_stats_fold")
+
+    def stats_enabled(self):
+        """Whether the batch statistics are on (set_grid turns them off)."""
+        return lib().lt_stats_batches(self._h, C.byref(C.c_uint64())) == 0
+
+    def stats_batches(self):
+        """Batches closed since the statistics were turned on or the tally was zeroed."""
+        n = C.c_uint64()
+        self._ck(lib().lt_stats_batches(self._h, C.byref(n)), "lt_stats_batches")
+        return n.value
+
+    def stats_m2(self):
+        """float64 [nz, ny, nx]: the sum over the closed batches of the squared batch contribution."""
+        out = np.empty(self._grid_shape or (0, 0, 0), dtype=np.float64)
+        self._ck(lib().lt_stats_read_m2(self._h, _dp(out), out.size), "lt_stats_read_m2")
+        return out
+
+    def stats_relerr(self):
+        """float64 [nz, ny, nx]: the relative standard error of every voxel (relative_error), NaN where it holds nothing."""
+        out = np.empty(self._grid_shape or (0, 0, 0), dtype=np.float64)
+        self._ck(lib().lt_stats_read_relerr(self._h, _dp(out), out.size), "lt_stats_read_relerr")
+        return out
+
+    def stats_summary(self, edges, raw=False):
+        """(voxels uint64, weight) per error class, [len(edges) + 2] each: class k = the voxels whose relative error has k of
+        the ascending ``edges`` at or below it, the last entry the voxels that hold nothing.  raw=True (u64 fixed-point tally
+        only): weight is the exact uint64 sums."""
+        e = _f64(edges).reshape(-1)
+        vox = np.zeros(e.size + 2, dtype=np.uint64)
+        out, rawbuf, rp = self._sum_buffers((e.size + 2,), raw)
+        self._ck(lib().lt_stats_summary(self._h, _dp(e), int(e.size), vox.ctypes.data_as(_U64P), _dp(out), rp), "lt_stats_summary")
+        return vox, (rawbuf if raw else out)
 
     def read_counters(self):
         c = Counters()

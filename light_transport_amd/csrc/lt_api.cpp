@@ -136,6 +136,12 @@ struct lt_ctx {
     bool dmap_valid = false, tile_cnt_ready = false, last_hot = false;
     uint32_t dmap_tiles = 0, dmap_bits2 = 0;      // the partition geometry the map was made for
     bool tables_dirty = true, media_dirty = false;
+    // statistics of the tally (lt_stats_*): the grid at the last fold, the second moments, closed batches; grid_touched: something
+    // was launched into or written to the grid since the last lt_set_grid / lt_zero_tally
+    DevBuf d_stat_prev, d_stat_m2;
+    bool stats_on = false, grid_touched = false;
+    uint64_t stats_batches = 0;
+    void stats_off() { d_stat_prev.release(); d_stat_m2.release(); stats_on = false; stats_batches = 0; }
     // Experiment knobs (lt_set_tuning; -1 = built-in default).  The environment variable LT_<KEY IN CAPITALS> seeds each of
     // them ONCE, in lt_create: nothing in this library reads the environment after that.
     struct Knobs {
@@ -1075,7 +1081,7 @@ int lt_destroy(lt_ctx* c)
     c->d_scratch_in.release(); c->d_scratch_out.release(); c->d_scratch_aux.release();
     c->d_mats.release(); c->d_lights.release(); c->d_r0.release(); c->d_r1.release(); c->d_lc.release();
     c->d_img.release(); c->d_xy.release(); c->d_vtx.release(); c->d_vcnt.release(); c->d_clear.release();
-    c->d_job.release(); c->d_dmap.release(); c->d_dmeta.release();
+    c->d_job.release(); c->d_dmap.release(); c->d_dmeta.release(); c->stats_off();
     c->d_mcell.release(); c->d_mlist.release(); c->d_mcoarse.release(); c->d_links.release();
     for (int k = 1; k < kMaxLanes; k++) { c->d_gridx[k - 1].release(); if (c->lanes[k].stream) (void)hipStreamSynchronize(c->lanes[k].stream); }
     for (int k = 0; k < kMaxLanes; k++) {
@@ -1178,6 +1184,7 @@ int lt_set_grid(lt_ctx* c, int nx, int ny, int nz, const double origin[3], const
         if (!(voxel[k] > 0) || !std::isfinite(origin[k])) return c->fail(LT_E_INVALID, "lt_set_grid: bad origin/voxel");
     if ((double)nx * ny * nz > 2147483647.0) return c->fail(LT_E_UNSUPPORTED, "lt_set_grid: more than 2^31-1 voxels");
     BIND(c);
+    if (c->stats_on) { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->stats_off(); }     // the moments belonged to the old grid
     c->nx = nx; c->ny = ny; c->nz = nz; c->tally = tally_dtype;
     for (int k = 0; k < 3; k++) { c->origin[k] = origin[k]; c->voxel[k] = voxel[k]; }
     HIP_TRY(c, c->d_grid.ensure(c->n_vox() * c->grid_elem()));
@@ -1244,6 +1251,12 @@ int lt_zero_tally(lt_ctx* c)
     BIND(c);
     if (c->have_grid) HIP_TRY(c, hipMemsetAsync(c->d_grid.p, 0, c->n_vox() * c->grid_elem(), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(DevCounters), c->stream));
+    c->grid_touched = false;
+    if (c->stats_on) {
+        HIP_TRY(c, hipMemsetAsync(c->d_stat_prev.p, 0, c->n_vox() * c->grid_elem(), c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_stat_m2.p, 0, c->n_vox() * sizeof(double), c->stream));
+        c->stats_batches = 0;
+    }
     return LT_OK;
 }
 
@@ -1280,6 +1293,7 @@ int lt_launch(lt_ctx* c, uint64_t n_photons, uint64_t photon_offset, uint64_t se
     int rc = upload_tables(c);
     if (rc) return rc;
     if (n_photons == 0) { c->timed = false; return LT_OK; }
+    c->grid_touched = true;
 
     if (v.table) {
         const size_t bytes = (size_t)n_photons * (size_t)table_steps * 4 * sizeof(double);
@@ -1579,6 +1593,7 @@ int lt_write_grid(lt_ctx* c, const void* host_in, size_t bytes)
     if (!host_in || bytes != c->n_vox() * c->grid_elem())
         return c->fail(LT_E_INVALID, "lt_write_grid: expected %zu bytes", c->n_vox() * c->grid_elem());
     BIND(c);
+    c->grid_touched = true;
     HIP_TRY(c, hipMemcpyAsync(c->d_grid.p, host_in, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return LT_OK;
@@ -1653,6 +1668,7 @@ int lt_reduce_grid(lt_ctx* c, void* comm, int root)
     if (!g_rccl.allreduce || !g_rccl.reduce || !g_rccl.gstart || !g_rccl.gend)
         return c->fail(LT_E_UNSUPPORTED, "lt_reduce_grid: librccl.so lacks ncclAllReduce/ncclReduce");
     BIND(c);
+    c->grid_touched = true;
     const int dt = c->tally == LT_TALLY_F32 ? kNcclFloat32 : (c->tally == LT_TALLY_F64 ? kNcclFloat64 : kNcclUint64);
     DevCounters* dc = (DevCounters*)c->d_counters.p;
     int rc = g_rccl.gstart();
@@ -1742,6 +1758,103 @@ int lt_tally_sum_columns(lt_ctx* c, const int32_t* bin_of_column, int n_bins, do
                                         c->stream));
     // the copy of the table has left the caller's array when this returns: sum_read_back waits for the stream
     return sum_read_back(c, n_out, out, raw_out);
+}
+
+// ---- statistical error of the tally from batch moments (kernels: lt_tallystats.hip) ----
+#define STATS_ON(c, who) do { if (!(c)->stats_on) return (c)->fail(LT_E_STATE, "%s: statistics are off (lt_stats_enable)", who); } while (0)
+
+int lt_stats_enable(lt_ctx* c, int on)
+{
+    CHECK_CTX(c);
+    BIND(c);
+    if (!on) {
+        if (c->stats_on) HIP_TRY(c, hipStreamSynchronize(c->stream));      // a fold may still be using the buffers
+        c->stats_off();
+        return LT_OK;
+    }
+    if (!c->have_grid) return c->fail(LT_E_STATE, "lt_stats_enable: no grid");
+    if (c->grid_touched)
+        return c->fail(LT_E_STATE, "lt_stats_enable: the grid was launched into or written to since the last lt_set_grid / lt_zero_tally");
+    if (c->d_stat_prev.ensure(c->n_vox() * c->grid_elem()) != hipSuccess || c->d_stat_m2.ensure(c->n_vox() * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        c->stats_off();
+        return c->fail(LT_E_NOMEM, "lt_stats_enable: no device memory for %zu more bytes", c->n_vox() * (c->grid_elem() + sizeof(double)));
+    }
+    c->stats_on = true; c->stats_batches = 0;
+    HIP_TRY(c, hipMemsetAsync(c->d_stat_prev.p, 0, c->n_vox() * c->grid_elem(), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_stat_m2.p, 0, c->n_vox() * sizeof(double), c->stream));
+    return LT_OK;
+}
+
+int lt_stats_fold(lt_ctx* c)
+{
+    CHECK_CTX(c);
+    STATS_ON(c, "lt_stats_fold");
+    BIND(c);
+    HIP_TRY(c, launch_stats_fold(c->d_grid.p, c->d_stat_prev.p, (double*)c->d_stat_m2.p, c->tally, c->n_vox(), c->stream));
+    c->stats_batches++;
+    return LT_OK;
+}
+
+int lt_stats_batches(lt_ctx* c, uint64_t* n_out)
+{
+    CHECK_CTX(c);
+    STATS_ON(c, "lt_stats_batches");
+    if (!n_out) return c->fail(LT_E_INVALID, "lt_stats_batches: null output");
+    *n_out = c->stats_batches;
+    return LT_OK;
+}
+
+int lt_stats_read_m2(lt_ctx* c, double* out, size_t n_voxels)
+{
+    CHECK_CTX(c);
+    STATS_ON(c, "lt_stats_read_m2");
+    if (!out || n_voxels != c->n_vox()) return c->fail(LT_E_INVALID, "lt_stats_read_m2: expected %zu voxels", c->n_vox());
+    BIND(c);
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_stat_m2.p, n_voxels * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return LT_OK;
+}
+
+int lt_stats_read_relerr(lt_ctx* c, double* out, size_t n_voxels)
+{
+    CHECK_CTX(c);
+    STATS_ON(c, "lt_stats_read_relerr");
+    if (!out || n_voxels != c->n_vox()) return c->fail(LT_E_INVALID, "lt_stats_read_relerr: expected %zu voxels", c->n_vox());
+    if (c->stats_batches < 2) return c->fail(LT_E_STATE, "lt_stats_read_relerr: %llu batches closed, the estimate needs two", (unsigned long long)c->stats_batches);
+    BIND(c);
+    HIP_TRY(c, c->d_scratch_out.ensure(n_voxels * sizeof(double)));
+    HIP_TRY(c, launch_stats_relerr(c->d_stat_prev.p, (const double*)c->d_stat_m2.p, c->tally, n_voxels, c->stats_batches,
+                                   (double*)c->d_scratch_out.p, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch_out.p, n_voxels * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return LT_OK;
+}
+
+int lt_stats_summary(lt_ctx* c, const double* edges, int n_edges, uint64_t* voxels_out, double* weight_out, uint64_t* raw_weight_out)
+{
+    CHECK_CTX(c);
+    STATS_ON(c, "lt_stats_summary");
+    if (!edges || !voxels_out || !weight_out) return c->fail(LT_E_INVALID, "lt_stats_summary: edges, voxels_out and weight_out are required");
+    if (raw_weight_out && c->tally != LT_TALLY_U64FX) return c->fail(LT_E_INVALID, "lt_stats_summary: raw_weight_out needs the LT_TALLY_U64FX tally");
+    if (n_edges < 1) return c->fail(LT_E_INVALID, "lt_stats_summary: need at least one edge");
+    if (n_edges > kMaxStatEdges) return c->fail(LT_E_UNSUPPORTED, "lt_stats_summary: %d edges, at most %d (the classes are counted in LDS)", n_edges, kMaxStatEdges);
+    for (int i = 0; i < n_edges; i++)
+        if (!std::isfinite(edges[i]) || edges[i] < 0.0 || (i > 0 && !(edges[i] > edges[i - 1])))
+            return c->fail(LT_E_INVALID, "lt_stats_summary: edges must be finite, >= 0 and strictly ascending (edge %d)", i);
+    if (c->stats_batches < 2) return c->fail(LT_E_STATE, "lt_stats_summary: %llu batches closed, the estimate needs two", (unsigned long long)c->stats_batches);
+    BIND(c);
+    const size_t n_cls = (size_t)n_edges + 2;
+    HIP_TRY(c, c->d_scratch_in.ensure((size_t)stats_summary_parts(c->n_vox(), c->tally) * n_cls * 16));
+    HIP_TRY(c, c->d_scratch_out.ensure(n_cls * 32));
+    char* d_out = (char*)c->d_scratch_out.p;
+    HIP_TRY(c, launch_stats_summary(c->d_stat_prev.p, (const double*)c->d_stat_m2.p, c->tally, c->n_vox(), c->stats_batches, edges, n_edges,
+                                    c->d_scratch_in.p, (double*)d_out, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(weight_out, d_out, n_cls * 8, hipMemcpyDeviceToHost, c->stream));
+    if (raw_weight_out) HIP_TRY(c, hipMemcpyAsync(raw_weight_out, d_out + n_cls * 8, n_cls * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(voxels_out, d_out + n_cls * 16, n_cls * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return LT_OK;
 }
 
 int lt_radial_bins(int nx, int ny, const double origin_xy[2], const double voxel_xy[2], const double centre_xy[2], double dr, int nr,

@@ -339,5 +339,20 @@ constexpr int kMaxSumBins = 4096;    // the bins of a column sum live in LDS, 8 
 size_t tally_sum_columns_plan(int nx, int ny, int nz, int n_bins);   // returns partial_bytes; n_out = nz * n_bins
 hipError_t launch_tally_sum_columns(const void* grid, int tally, int nx, int ny, int nz, const int32_t* bins, int n_bins, void* partials,
                                     double* out, unsigned long long* raw, hipStream_t s);
+// the finishing pass of those sums on its own: out[i] = partial[0][i] + ... + partial[P - 1][i] in a fixed order; partial
+// [P][n_out] u64 (integer != 0: out = sum * 2^-40, raw -- may be null -- the sum) or f64 (raw is not used)
+hipError_t launch_tally_sum_finish(const void* partial, int integer, uint32_t P, size_t n_out, double* out, unsigned long long* raw,
+                                   hipStream_t s);
+
+// Statistical error of the tally from batch moments (lt_tallystats.hip).  prev: the grid at the last fold, in the tally's type;
+// m2: f64 per voxel.  The summary goes through stats_summary_parts(...) x (n_edges + 2) x 16 bytes of partial sums and leaves
+// in `out`, n_edges + 2 8-byte words each: the weight per class (f64), the raw weight (u64 fixed point only), the voxels (u64),
+// and one more block that is not used.  edges: host array, checked by the caller (finite, >= 0, ascending, 1 .. kMaxStatEdges).
+constexpr int kMaxStatEdges = 63;
+hipError_t launch_stats_fold(const void* grid, void* prev, double* m2, int tally, size_t n, hipStream_t s);
+hipError_t launch_stats_relerr(const void* prev, const double* m2, int tally, size_t n, uint64_t batches, double* out, hipStream_t s);
+uint32_t stats_summary_parts(size_t n_vox, int tally);
+hipError_t launch_stats_summary(const void* prev, const double* m2, int tally, size_t n, uint64_t batches, const double* edges,
+                                int n_edges, void* partials, double* out, hipStream_t s);
 
 }  // namespace ltk

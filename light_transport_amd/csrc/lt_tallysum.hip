@@ -331,4 +331,12 @@ hipError_t launch_tally_sum_columns(const void* grid, int tally, int nx, int ny,
     return hipGetLastError();
 }
 
+hipError_t launch_tally_sum_finish(const void* partial, int integer, uint32_t P, size_t n_out, double* out, unsigned long long* raw,
+                                   hipStream_t s)
+{
+    if (integer) run_finish<u64>((const u64*)partial, P, n_out, out, raw, s);
+    else run_finish<double>((const double*)partial, P, n_out, out, nullptr, s);
+    return hipGetLastError();
+}
+
 }  // namespace ltk

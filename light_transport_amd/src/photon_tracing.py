@@ -106,6 +106,7 @@ class PhotonTracer:
         self.grid = None
         self.quantity = "absorbed"
         self.photons = 0          # traced since the last reset (the fluence normalisation)
+        self._profiles = {}       # run_batches: keep mask -> [batches, sum of the per-batch sums, sum of their squares]
 
     def configure(self, geometry, grid, source, primitives=None, linear_bvh=None, max_steps=None, quantity="absorbed"):
         ctx = self.ctx
@@ -140,6 +141,7 @@ class PhotonTracer:
         ctx.set_vertex_capture(0)
         ctx.set_tally_quantity(quantity)     # "absorbed": weight absorbed per voxel; "fluence": w / mu_t per interaction
         self.grid, self.quantity, self.photons = grid, quantity, 0
+        self._profiles = {}
         return self
 
     def run(self, n_photons, seed=0, photon_offset=0, rng_table=None, f32_walk=False, wait=True):
@@ -149,9 +151,66 @@ class PhotonTracer:
             self.ctx.sync()
         return self
 
+    def run_batches(self, n_photons, n_batches, seed=0, photon_offset=0, f32_walk=False, profiles=()):
+        """``n_photons`` traced as ``n_batches`` consecutive id ranges of equal size, every one closed with a fold of the batch
+        statistics (turned on here if they are off): the grid ends as run(n_photons) leaves it, and relative_error() /
+        error_summary() say how far every voxel can be trusted.  ``profiles``: keep-strings as tally_sum takes them ("z": the
+        depth profile); for each, the device sum is taken after every fold and the moments of the per-batch differences are
+        kept on the host for profile_error() -- voxels of one batch are correlated, so the error of a sum does not follow
+        from the per-voxel moments."""
+        n_photons, n_batches = int(n_photons), int(n_batches)
+        if n_batches < 2 or n_photons % n_batches:
+            raise ValueError("run_batches: n_batches = %d must be at least 2 and divide n_photons = %d (equal batches)" % (n_batches, n_photons))
+        masks = [_lib.keep_mask(k) for k in profiles]
+        ctx = self.ctx
+        if not ctx.stats_enabled():
+            ctx.stats_enable(True)
+            self._profiles = {}
+        raw = self.grid.dtype in ("u64fx", _lib.TALLY["u64fx"])
+        last = {}
+        for m in masks:      # where the profile stands before the first batch (zero, unless earlier batches were run)
+            last[m] = ctx.tally_sum(m, raw=raw)
+            if m not in self._profiles:
+                self._profiles[m] = [0, np.zeros(last[m].shape), np.zeros(last[m].shape)]
+        per = n_photons // n_batches
+        for b in range(n_batches):
+            ctx.launch(per, seed=seed, photon_offset=int(photon_offset) + b * per, f32_walk=f32_walk)
+            ctx.stats_fold()
+            for m in masks:
+                now = ctx.tally_sum(m, raw=raw)
+                d = (now - last[m]).astype(np.float64) * 2.0 ** -40 if raw else now - last[m]
+                mom = self._profiles[m]
+                mom[0] += 1
+                mom[1] = mom[1] + d
+                mom[2] = mom[2] + d * d
+                last[m] = now
+        self.photons += n_photons
+        ctx.sync()
+        return self
+
+    def relative_error(self):
+        """float64 [nz, ny, nx]: relative standard error of every voxel over the batches of run_batches (NaN where the voxel
+        holds nothing; 1 where a single batch contributed)."""
+        return self.ctx.stats_relerr()
+
+    def error_summary(self, edges):
+        """(voxels, weight) per class of relative error, [len(edges) + 2] each (Context.stats_summary): weight[0] is what
+        the voxels below edges[0] hold, the last entry the empty voxels.  Taken on the device: no grid is read back."""
+        return self.ctx.stats_summary(edges)
+
+    def profile_error(self, keep):
+        """The relative standard error of tally_sum(keep) over the batches (same shape), from the moments run_batches kept
+        for a ``profiles`` entry: _lib.relative_error(batches, sum, sum of squares)."""
+        m = _lib.keep_mask(keep)
+        if m not in self._profiles:
+            raise ValueError("profile_error(%r): run_batches(..., profiles=(%r,)) first" % (keep, keep))
+        n, s1, s2 = self._profiles[m]
+        return _lib.relative_error(n, s1, s2)
+
     def reset(self):
         self.ctx.zero_tally()
         self.photons = 0
+        self._profiles = {}
 
     def absorbed(self):
         """float64 [nz, ny, nx]: absorbed photon weight per voxel (configure(..., quantity="absorbed"))."""
