@@ -29,6 +29,7 @@
 //
 // Reference citations: S/ = LightTransportSimulator/light_transport/src/.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 #define ROCRAND_DETAIL_BM_NOT_IN_STATE
 #include <rocrand/rocrand_xorwow.h>
@@ -1223,6 +1224,17 @@ LT_DEV unsigned long long readlane64(unsigned long long v, int lane)
     return ((unsigned long long)hi << 32) | lo;
 }
 
+// a * b + c for a, b < 2^24 (b wave-uniform) as v_mad_u32_u24.  The instruction is named because the compiler cannot be told:
+// it does not know the factors' ranges, and where only the low bits of the result are kept it drops a mask on them (and HIP's
+// __umul24 with it) and multiplies in 32 bits -- v_mad_u64_u32, with a 64-bit addend and result.  Both issue at 1.7 x the
+// price of an integer add (tools/probes/int_mul_rate_probe.hip): the 24-bit form saves the register pairs, not issue time.
+LT_DEV unsigned mad_u24(unsigned a, unsigned b, unsigned c)
+{
+    unsigned r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
+    return r;
+}
+
 template <typename T> LT_DEV T wave_sum(T v)
 {
 #pragma unroll
@@ -1251,17 +1263,25 @@ LT_DEV void record_vertex(const WalkParams& P, unsigned long long rel, unsigned&
 // global atomic.  Log mode: the wave's records are compacted by ballot rank and appended, coalesced, to the wave's
 // current log chunk (SoA: voxel index, value); a chunk is claimed with one returning atomic per kLogChunk records.
 // If the log is exhausted the wave falls back to atomics, so a too-small log costs speed, never correctness.
+// A lane without a record passes idx == kNoVoxel (its val is then not read).  IDX_MASK (the slab walks): the wave's mask of
+// records is the ballot of that integer compare, taken in front of the tally-mode branch: there it IS the compare's result (one
+// v_cmp into a scalar pair).  Taken from the bool behind the branch (the mesh walks, which have no scalar pair to carry it in) it
+// costs a round trip through a VGPR (v_cndmask 0,1 + v_cmp_ne) in every wave-step.
 constexpr unsigned kLogExhausted = 0xfffffffeu;   // lg_chunk: this wave has found the log full (0xffffffff: no chunk claimed yet)
-template <int TALLY>
-LT_DEV void emit_deposit(const WalkParams& P, bool has, unsigned idx, typename TallyT<TALLY>::type val,
+constexpr unsigned kNoVoxel = 0xffffffffu;        // idx: no record
+template <int TALLY, bool IDX_MASK>
+LT_DEV void emit_deposit(const WalkParams& P, unsigned idx, typename TallyT<TALLY>::type val,
                          unsigned& lg_cur, unsigned& lg_end, unsigned& lg_chunk, uint32_t* s_hist)
 {
     typedef typename TallyT<TALLY>::type TV;
+    const bool has = idx != kNoVoxel;
+    unsigned long long m = 0;
+    if constexpr (IDX_MASK) m = __ballot(has);
     if (P.log_idx == nullptr) {
         if (has) tally_add<TALLY>(P.grid, idx, val);
         return;
     }
-    const unsigned long long m = __ballot(has);
+    if constexpr (!IDX_MASK) m = __ballot(has);
     if (m == 0ull) return;
     const unsigned cnt = (unsigned)__popcll(m);
     // (a wave that has found the log exhausted does not ask again: lg_chunk == kLogExhausted is sticky, so an undersized log

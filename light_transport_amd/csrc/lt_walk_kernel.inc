@@ -51,6 +51,14 @@ __attribute__((amdgpu_num_vgpr(LT_SLAB_VGPR_CAP)))      // measurement builds: t
 __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLAB_WAVES : (GEOM == 2 ? LT_F64_GLOBAL_WAVES : LT_F64_WAVES)) : (GEOM == 0 ? LT_F32_WAVES : 4))) LT_WALK_NAME(const WalkParams P)
 {
     constexpr bool MESH = GEOM != 0;
+    // Wave bookkeeping off the vector pipe (profiles/r07a_walk_bookkeeping.log).  kSlabForm, every slab walk: the 32-bit packet
+    // cursor, the refill count as a 32-bit scalar, the deposit mask taken on the index compare (emit_deposit), the tile index by
+    // mad_u24.  kLean: the two forms that lengthen a value's life -- `need` kept to the loop's exit, f_val without a default.  The
+    // tail kernel (PHASE 2) takes them too: 84-88 VGPRs where it had 84-86, the same five waves per SIMD.  The vertex capture does
+    // not (it spilled 20-28 B), nor do the mesh walks take any of these forms: they sit at their register limits, and the log has
+    // the register and scratch figures of the mesh kernels built with all of them and with the 32-bit cursor alone.
+    constexpr bool kSlabForm = LT_WALK_BATCH == 0;
+    constexpr bool kLean = kSlabForm && !CAPTURE;
 #if LT_WALK_BATCH == 2
     constexpr int PHASE = 0;
 #endif
@@ -128,13 +136,17 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
     // run-length accumulation: consecutive deposits into the same voxel (a third of all steps when the
     // voxel is one mean free path wide) are summed in registers and sent as ONE atomic request
     typedef typename TallyT<TALLY>::type TV;
-    constexpr unsigned kNoVoxel = 0xffffffffu;
     unsigned pend_idx = kNoVoxel;
     TV pend_val = 0;
     // wave-level deposit-log cursor (log mode): records [lg_cur, lg_end) of chunk lg_chunk are free
     unsigned lg_cur = 0, lg_end = 0, lg_chunk = kNoVoxel;
-    // wave-level packet of photon ids [pk_next, pk_end)
-    unsigned long long pk_next = 0, pk_end = 0;
+    // wave-level packet of photon ids [pk_base + pk_next, pk_base + pk_end).  Slab walks: a packet is at most kPacket ids, so
+    // the cursor is a pair of 32-bit offsets that the scalar unit compares (it has no ordered 64-bit compare: each would be a
+    // v_mov_b64 + v_cmp_*_u64 on the vector pipe, in every wave-step that has a dead lane), and only the base is 64 bits wide.
+    // Mesh walks: the offsets are the ids themselves and the base stays 0 (the 32-bit form costs those kernels a register).
+    typedef typename std::conditional<kSlabForm, unsigned, unsigned long long>::type pk_t;
+    unsigned long long pk_base = 0;
+    pk_t pk_next = 0, pk_end = 0;
     bool q_done = false;
     bool dumped = false;      // PHASE 1: this wave has handed its last photons to the pool
 #if LT_WALK_BATCH
@@ -219,18 +231,24 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
         // take part, and some lane dies in one wave-step out of five: waiting until kRefillMin lanes are free cuts that
         // overhead fourfold for an average of 1.5 idle lanes.  A photon's fate depends on (seed, id) only, so the
         // results do not change.
+        // `alive` lives as a lane mask in a scalar pair, and every ballot of it is a round trip through a VGPR (v_cndmask 0,1 +
+        // v_cmp_ne): it is taken ONCE per iteration, here, and the refill test and the loop's exit both read `need`; the two
+        // rare blocks that change `alive` after it -- a refill, a hand-over -- ask again.
         unsigned long long need = __ballot(!alive);
-        if (need != 0ull && !(q_done && pk_next >= pk_end) &&
-            ((unsigned)__popcll(need) >= kRefillMin || need == __ballot(true))) {
-            const unsigned cnt = (unsigned)__popcll(need);
+        // (the count goes through an empty asm as a 32-bit scalar: left visible, `popcount >= kRefillMin` is widened to a 64-bit
+        // ordered compare, which the scalar unit does not have -- v_mov_b64 + v_cmp_*_u64 on the vector pipe)
+        unsigned cnt = (unsigned)__popcll(need);
+        if constexpr (kSlabForm) asm("" : "+s"(cnt));
+        if (need != 0ull && !(q_done && pk_next >= pk_end) && (cnt >= kRefillMin || need == __ballot(true))) {
 #if LT_WALK_BATCH && defined(LT_DIAG_MESH)
             dg_refill_it++; dg_refill += cnt;
 #endif
             const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(need >> 32),
                                       __builtin_amdgcn_mbcnt_lo((unsigned)need, 0u));
-            const unsigned long long avail = pk_end - pk_next;
-            unsigned long long nlo = 0, nhi = 0;
-            if (cnt > avail && !q_done) {
+            const pk_t avail = pk_end - pk_next;
+            unsigned long long nlo = 0, nhi = 0;     // a packet taken from the queue now: ids [nlo, nhi), nnew of them
+            pk_t nnew = 0;
+            if (cnt > avail && !q_done) {   // the rare dequeue: the only 64-bit arithmetic of the refill
                 const int leader = __ffsll((long long)need) - 1;
                 unsigned long long base = 0;
                 if (lane == leader)
@@ -239,19 +257,20 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                 base = readlane64(base, leader);
                 nlo = base < P.n_photons ? base : P.n_photons;
                 nhi = base + kPacket < P.n_photons ? base + kPacket : P.n_photons;
+                nnew = (pk_t)(nhi - nlo);
                 if (nhi >= P.n_photons) q_done = true;
             }
             bool got = false;
             unsigned long long id = 0;
             if (!alive) {
-                if (rank < avail) { id = pk_next + rank; got = true; }
-                else if (rank - avail < nhi - nlo) { id = nlo + (rank - avail); got = true; }
+                if (rank < avail) { id = pk_base + (pk_next + rank); got = true; }
+                else if (rank - avail < nnew) { id = nlo + (rank - avail); got = true; }
             }
             if (cnt <= avail) pk_next += cnt;
             else {
-                unsigned long long used = cnt - avail;
-                if (used > nhi - nlo) used = nhi - nlo;
-                pk_next = nlo + used; pk_end = nhi;
+                const pk_t used = cnt - avail < nnew ? cnt - avail : nnew;
+                if constexpr (kSlabForm) { pk_base = nlo; pk_next = used; pk_end = nnew; }
+                else { pk_next = nlo + used; pk_end = nhi; }
             }
 
             if (got) {
@@ -327,14 +346,19 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                     if (cap < (unsigned long long)max_steps) max_steps = (unsigned)cap;
                 }
             }
+            need = __ballot(!alive);
         }
+        // wave-uniform: queue drained and every lane done (the right-hand side is exec).  In front of the hand-over, which does
+        // nothing for a wave without a live lane: kept beyond it, `need` costs the bulk kernel a scalar pair it does not have (the
+        // log's pointers were spilled instead, and restored in every append).  The kernels that are not kLean ask `alive` again, below.
+        if constexpr (kLean) if (need == __ballot(true)) break;
         if constexpr (PHASE == 1) {
             // bulk: nothing left to refill with and few lanes alive -> hand them over and leave (see "Tail split" above)
             if (q_done && pk_next >= pk_end && !dumped) {
                 const unsigned long long am = __ballot(alive);
                 const unsigned na = (unsigned)__popcll(am);
                 if (na != 0u && na <= P.dump_max) {
-                    emit_deposit<TALLY>(P, pend_idx != kNoVoxel, pend_idx, pend_val, lg_cur, lg_end, lg_chunk, s_hist);
+                    emit_deposit<TALLY, kSlabForm>(P, pend_idx, pend_val, lg_cur, lg_end, lg_chunk, s_hist);
                     pend_idx = kNoVoxel;
                     const int leader = __ffsll((long long)am) - 1;
                     unsigned base = 0;
@@ -361,10 +385,11 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                         }
                     }
                     dumped = true;
+                    if constexpr (kLean) if (!__any(alive)) break;
                 }
             }
         }
-        if (!__any(alive)) break;  // wave-uniform: queue drained and every lane done
+        if constexpr (!kLean) if (!__any(alive)) break;  // wave-uniform: queue drained and every lane done
 
 #if LT_WALK_BATCH == 2
         // ---------------- one photon-step ----------------
@@ -626,7 +651,11 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
 #else
         // ---------------- one photon-step ----------------
         unsigned f_idx = kNoVoxel;  // deposit record leaving the run-length accumulator this step
-        TV f_val = 0;
+        // Its value is read only where f_idx names a voxel.  A default would be written on every path of the step that does not
+        // set it (three per wave-step in the ISA), so it is defined without code, by an empty asm with an output only.  (Not the
+        // vertex capture, nor the mesh kernels: there the definition's longer life costs a register they do not have.)
+        TV f_val;
+        if constexpr (kLean) asm volatile("" : "=v"(f_val)); else f_val = 0;
         if (alive) {
             if (step >= max_steps) {
                 atomicAdd(&s_cnt[CW_CAPPED], (double)w); alive = false;
@@ -794,9 +823,15 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                     if constexpr (!MESH) inside = (int)(Mx<R>::sign_word(fx) | Mx<R>::sign_word(fy) | Mx<R>::sign_word(fz)) >= 0 &&
                                                   vx < (unsigned)P.nx && vy < (unsigned)P.ny && vz < (unsigned)P.nz;
                     else inside = fx >= 0 && fx < fnx && fy >= 0 && fy < fny && fz >= 0 && fz < fnz;
+                    // the tile of the voxel (log mode).  <= 65536 tiles, so on a lane inside the grid every factor and sum is below
+                    // 2^24 (a lane outside it gets a meaningless index, which is not used).  Slab walks: two v_mad_u32_u24 (mad_u24).
+                    // Mesh walks: __umul24 compiles to two v_mad_u64_u32 here -- the compiler keeps only the low 18 bits of the
+                    // product and with that forgets the factors' width; the probe prices the two forms alike.
+                    unsigned tile;
+                    if constexpr (kSlabForm) tile = mad_u24(mad_u24(vz >> kTileBZ, P.log_nty, vy >> kTileBY), P.log_ntx, vx >> kTileBX);
+                    else tile = __umul24(__umul24(vz >> kTileBZ, P.log_nty) + (vy >> kTileBY), P.log_ntx) + (vx >> kTileBX);
                     const unsigned idx = P.log_idx   // log mode: tiled index (see kTileBX); atomic mode: linear index
-                        ? (((__umul24(__umul24(vz >> kTileBZ, P.log_nty) + (vy >> kTileBY), P.log_ntx) + (vx >> kTileBX)) << kTileShift)      // (<= 65536 tiles: 24-bit products, full rate)
-                           | ((vz & 15u) << 10) | ((vy & 31u) << 5) | (vx & 31u))
+                        ? ((tile << kTileShift) | ((vz & 15u) << 10) | ((vy & 31u) << 5) | (vx & 31u))
                         : (vz * (unsigned)P.ny + vy) * (unsigned)P.nx + vx;
                     const TV q = tally_quantum<TALLY, R>(w * LT_STEP_DEP);     // the tally quantity: absorbed weight, or w / mu_t (fluence)
                     const bool same = inside && idx == pend_idx;
@@ -830,9 +865,9 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
         dg_clk_bnd += clock64() - dg_t1;
 #endif
         // wave-uniform point: send this step's records to the grid (atomics) or to the deposit log
-        emit_deposit<TALLY>(P, f_idx != kNoVoxel, f_idx, f_val, lg_cur, lg_end, lg_chunk, s_hist);
+        emit_deposit<TALLY, kSlabForm>(P, f_idx, f_val, lg_cur, lg_end, lg_chunk, s_hist);
     }
-    emit_deposit<TALLY>(P, pend_idx != kNoVoxel, pend_idx, pend_val, lg_cur, lg_end, lg_chunk, s_hist);
+    emit_deposit<TALLY, kSlabForm>(P, pend_idx, pend_val, lg_cur, lg_end, lg_chunk, s_hist);
     if (P.log_idx && lg_chunk < kLogExhausted && (threadIdx.x & 63) == 0) P.log_fill[lg_chunk] = lg_cur - lg_chunk * kLogChunk;
 
 #if LT_WALK_BATCH && defined(LT_DIAG_MESH)

@@ -17,6 +17,12 @@ template <int OP> __global__ void k(unsigned* out, unsigned a, unsigned b, int n
         }
         if (OP == 4) { asm volatile("v_fma_f64 %0, %0, %0, %0" : "+v"(d0)); asm volatile("v_fma_f64 %0, %0, %0, %0" : "+v"(d1)); asm volatile("v_fma_f64 %0, %0, %0, %0" : "+v"(d2)); asm volatile("v_fma_f64 %0, %0, %0, %0" : "+v"(d3)); }
         if (OP == 5) { asm volatile("v_rsq_f64 %0, %0" : "+v"(d0)); asm volatile("v_rsq_f64 %0, %0" : "+v"(d1)); asm volatile("v_rsq_f64 %0, %0" : "+v"(d2)); asm volatile("v_rsq_f64 %0, %0" : "+v"(d3)); }
+        // a lane mask's round trip through a VGPR, as a ballot of a bool compiles: v_cndmask_b32 0, 1 + v_cmp_ne_u32 (two instructions per chain)
+        if (OP == 7) {
+            asm volatile("v_cndmask_b32 %0, 0, 1, vcc\n\tv_cmp_ne_u32 vcc, %1, %0" : "+v"(x0) : "v"(a) : "vcc"); asm volatile("v_cndmask_b32 %0, 0, 1, vcc\n\tv_cmp_ne_u32 vcc, %1, %0" : "+v"(x1) : "v"(a) : "vcc");
+            asm volatile("v_cndmask_b32 %0, 0, 1, vcc\n\tv_cmp_ne_u32 vcc, %1, %0" : "+v"(x2) : "v"(a) : "vcc"); asm volatile("v_cndmask_b32 %0, 0, 1, vcc\n\tv_cmp_ne_u32 vcc, %1, %0" : "+v"(x3) : "v"(a) : "vcc");
+        }
+        if (OP == 8) { asm volatile("v_mov_b64 %0, %1" : "+v"(y0) : "v"(y1)); asm volatile("v_mov_b64 %0, %1" : "+v"(y1) : "v"(y2)); asm volatile("v_mov_b64 %0, %1" : "+v"(y2) : "v"(y3)); asm volatile("v_mov_b64 %0, %1" : "+v"(y3) : "v"(y0)); }
         if (OP == 6) { asm volatile("v_cvt_f64_u32 %0, %1" : "+v"(d0) : "v"(x0)); asm volatile("v_cvt_f64_u32 %0, %1" : "+v"(d1) : "v"(x1)); asm volatile("v_cvt_f64_u32 %0, %1" : "+v"(d2) : "v"(x2)); asm volatile("v_cvt_f64_u32 %0, %1" : "+v"(d3) : "v"(x3)); }
     }
     out[blockIdx.x * blockDim.x + threadIdx.x] = x0 + x1 + x2 + x3 + (unsigned)(y0 + y1 + y2 + y3) + (unsigned)(d0 + d1 + d2 + d3);
@@ -32,8 +38,8 @@ int main()
 {
     unsigned* d; (void)hipMalloc(&d, 1024 * 256 * 4);
     const int n = 1 << 18;
-    const float t0 = run<0>(d, n), t1 = run<1>(d, n), t2 = run<2>(d, n), t3 = run<3>(d, n), t4 = run<4>(d, n), t5 = run<5>(d, n), t6 = run<6>(d, n);
-    printf("4 x n instructions per lane, 4 waves per SIMD: v_add_u32 %.2f ms | v_mul_lo_u32 %.2f (%.1fx) | v_mad_u32_u24 %.2f (%.1fx) | v_mad_u64_u32 %.2f (%.1fx) | v_fma_f64 %.2f (%.1fx) | v_rsq_f64 %.2f (%.1fx) | v_cvt_f64_u32 %.2f (%.1fx)\n",
-           t0, t1, t1 / t0, t2, t2 / t0, t3, t3 / t0, t4, t4 / t0, t5, t5 / t0, t6, t6 / t0);
+    const float t0 = run<0>(d, n), t1 = run<1>(d, n), t2 = run<2>(d, n), t3 = run<3>(d, n), t4 = run<4>(d, n), t5 = run<5>(d, n), t6 = run<6>(d, n), t7 = run<7>(d, n), t8 = run<8>(d, n);
+    printf("4 x n instructions per lane, 4 waves per SIMD: v_add_u32 %.2f ms | v_mul_lo_u32 %.2f (%.1fx) | v_mad_u32_u24 %.2f (%.1fx) | v_mad_u64_u32 %.2f (%.1fx) | v_fma_f64 %.2f (%.1fx) | v_rsq_f64 %.2f (%.1fx) | v_cvt_f64_u32 %.2f (%.1fx) | v_cndmask_b32 + v_cmp_ne_u32 %.2f (%.1fx, the pair) | v_mov_b64 %.2f (%.1fx)\n",
+           t0, t1, t1 / t0, t2, t2 / t0, t3, t3 / t0, t4, t4 / t0, t5, t5 / t0, t6, t6 / t0, t7, t7 / t0, t8, t8 / t0);
     return 0;
 }
