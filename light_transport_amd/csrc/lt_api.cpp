@@ -1285,7 +1285,7 @@ int lt_launch(lt_ctx* c, uint64_t n_photons, uint64_t photon_offset, uint64_t se
     v.capture = c->max_vertices > 0 ? 1 : 0;
     v.phase = 0;
     if (v.capture && (v.f32 || v.table)) return c->fail(LT_E_UNSUPPORTED, "lt_launch: vertex capture runs the f64 walk with the XORWOW generator");
-    if (c->on(c->knob.diag_no_tally)) v.tally = 3;  // diagnostic: time the walk without deposition
+    if (c->on(c->knob.diag_no_tally)) v.tally = LT_TALLY_NONE;  // diagnostic: time the walk without deposition
     if (v.table && v.f32) return c->fail(LT_E_UNSUPPORTED, "lt_launch: table RNG runs the f64 walk only");
     if (v.table && v.tally == LT_TALLY_F32) return c->fail(LT_E_UNSUPPORTED, "lt_launch: table RNG needs an f64 or u64fx tally");
     if (v.table && table_steps == 0) return c->fail(LT_E_INVALID, "lt_launch: table_steps == 0");

@@ -1,33 +1,8 @@
-// lt_kernels.hip -- gfx950 (CDNA4) kernels of the photon-transport hot path.
-//
-// Design:
-//   * one wavefront lane per live photon; photon state lives in VGPRs;
-//   * persistent threads: the grid is sized to the resident capacity of the
-//     chip and every wave loops, pulling PACKETS of photon ids from one global
-//     counter (1 returning atomic per 64 photons) -- divergent path lengths are
-//     absorbed by refilling dead lanes, not by launching more threads;
-//   * dead lanes are found with a wave ballot and refilled by ballot rank
-//     (v_mbcnt), four at a time (a refill costs the whole wave ~140 instructions);
-//   * rocRAND XORWOW state per lane, re-seeded per photon from (seed, id) and
-//     warmed up by 8 discarded outputs, so a photon's uniforms do not depend
-//     on which lane / wave / GPU traces it;
-//   * the kernel body lives in lt_walk_kernel.inc and is instantiated twice:
-//     walk_kernel (slabs) and walk_kernel_q (meshes: BVH queries batched per
-//     wave, the one divergent block expensive enough to be worth waiting for);
-//   * media, layer and BVH/triangle tables are staged once per workgroup into
-//     LDS (all lanes read the same few entries: LDS broadcast);
-//   * deposits: consecutive same-voxel deposits of a lane are merged in
-//     registers; the surviving records go either to the grid with no-return
-//     global atomics (f32 / f64 / u64 fixed point) or -- default for slabs --
-//     into a coalesced deposit log that lt_logtally.hip partitions by grid tile
-//     and reduces in LDS (the memory-side atomic unit, ~16e9 requests/s, was
-//     the limiter; HBM streaming bandwidth is not); rare per-photon events go
-//     to LDS counters;
-//   * f64 arithmetic (the reference's dtype) with lean -ln / sincos / sqrt /
-//     quotient primitives for the hot loop's restricted argument ranges.
-// No MFMA: there is no dense contraction anywhere on this path.
-//
+// lt_device.hpp -- the __device__ functions of lt_walk.hip, lt_query.hip and lt_render.hip (device-only, never the host glue's):
+// the lean f64 math primitives and their table, ray / triangle / BVH / march-grid intersection, the photon physics, the RNG
+// seeding.  All __forceinline__, and kWalkMathTab is const (internal linkage): every translation unit carries its own copy.
 // Reference citations: S/ = LightTransportSimulator/light_transport/src/.
+#pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
@@ -1158,1152 +1133,13 @@ LT_DEV void photon_stream(unsigned long long seed, unsigned long long photon_id,
     for (int k = 0; k < kRngWarmup; k++) (void)rocrand(st);
 }
 
-// ---------------------------------------------------------------------------
-// tally
-// ---------------------------------------------------------------------------
-// value type a deposit is accumulated in before it is sent to memory
-template <int TALLY> struct TallyT { typedef double type; };
-template <> struct TallyT<LT_TALLY_F32> { typedef float type; };
-template <> struct TallyT<LT_TALLY_U64FX> { typedef unsigned long long type; };
-#define LT_TALLY_NONE 3  /* diagnostic build of the walk without deposition (not part of the ABI) */
-
-template <int TALLY, typename R> LT_DEV typename TallyT<TALLY>::type tally_quantum(R dw)
-{
-    if constexpr (TALLY == LT_TALLY_U64FX) return (unsigned long long)((double)dw * LT_FX_SCALE + 0.5);
-    else return (typename TallyT<TALLY>::type)dw;
-}
-
-template <int TALLY> LT_DEV void tally_add(void* grid, unsigned idx, typename TallyT<TALLY>::type v)
-{
-    if constexpr (TALLY == LT_TALLY_NONE) { asm volatile("" ::"v"(idx), "v"(v)); }
-    else
-        __hip_atomic_fetch_add(reinterpret_cast<typename TallyT<TALLY>::type*>(grid) + idx, v, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---------------------------------------------------------------------------
-// LDS image of the scene tables
-// ---------------------------------------------------------------------------
-LT_DEV size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-template <typename R> struct LdsLayout {
-    size_t off_cnt, off_frame, off_media, off_zb, off_if, off_lm, off_lay, off_tris, off_nodes, off_links, off_hist, off_march, off_math, total;
-    __host__ __device__ LdsLayout(int n_media, int n_layers, int n_tris, int n_nodes, unsigned n_hist = 0, size_t march_bytes = 0)
-    {
-        auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-        size_t o = 0;
-        off_cnt = o;   o = al(o + 8 * sizeof(double));
-        off_frame = o; o = al(o + 15 * sizeof(R));     // frame of the source normal (area sources) + the grid's origin / inverse voxel / dimensions
-        off_media = o; o = al(o + (size_t)n_media * sizeof(MedD<R>));
-        off_zb = o;    o = al(o + (size_t)(n_layers + 1) * sizeof(R));
-        off_if = o;    o = al(o + (size_t)(n_layers > 0 ? n_layers + 1 : 0) * sizeof(IfD<R>));
-        off_lm = o;    o = al(o + (size_t)(n_layers > 0 ? n_layers : 1) * sizeof(int32_t));
-        off_lay = o;   o = al(o + (size_t)(n_layers > 0 ? n_layers : 0) * sizeof(LayD<R>));      // slab walks: the per-layer step records
-        off_tris = o;  o = al(o + (size_t)n_tris * sizeof(TriD<R>));
-        off_nodes = o; o = al(o + (size_t)n_nodes * sizeof(NodeD<R>));
-        off_links = o; o = al(o + (size_t)n_nodes * 16 * sizeof(int16_t));      // front-to-back link tables (8 patterns x first | after)
-        off_hist = o;  o = al(o + (size_t)n_hist * sizeof(uint32_t));
-        off_march = o; o = al(o + march_bytes);
-        off_math = o;  o = al(o + (sizeof(R) == 8 ? kWalkMathTabBytes : 0));      // f64 walks: kWalkMathTab
-        total = o;
-    }
-};
-
+// staging of scene tables in LDS (the walks and the renderer)
 LT_DEV void lds_copy(void* dst, const void* src, size_t bytes)
 {
     // tables are small (KBs); dword copies, all threads of the workgroup
     uint32_t* d = reinterpret_cast<uint32_t*>(dst);
     const uint32_t* s = reinterpret_cast<const uint32_t*>(src);
     for (size_t i = threadIdx.x; i < bytes / 4; i += blockDim.x) d[i] = s[i];
-}
-
-LT_DEV unsigned long long readlane64(unsigned long long v, int lane)
-{
-    unsigned lo = __builtin_amdgcn_readlane((unsigned)v, lane);
-    unsigned hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), lane);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// a * b + c for a, b < 2^24 (b wave-uniform) as v_mad_u32_u24.  The instruction is named because the compiler cannot be told:
-// it does not know the factors' ranges, and where only the low bits of the result are kept it drops a mask on them (and HIP's
-// __umul24 with it) and multiplies in 32 bits -- v_mad_u64_u32, with a 64-bit addend and result.  Both issue at 1.7 x the
-// price of an integer add (tools/probes/int_mul_rate_probe.hip): the 24-bit form saves the register pairs, not issue time.
-LT_DEV unsigned mad_u24(unsigned a, unsigned b, unsigned c)
-{
-    unsigned r;
-    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
-    return r;
-}
-
-template <typename T> LT_DEV T wave_sum(T v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// light sub-path capture (f4): store vertex k of photon `rel` while k < max_vertices
-template <typename R>
-LT_DEV void record_vertex(const WalkParams& P, unsigned long long rel, unsigned& nv, R px, R py, R pz, R ux, R uy,
-                          R uz, R w, int kind, int medium, unsigned step, R gx, R gy, R gz, R pdf_pos, R pdf_dir)
-{
-    if (nv < P.max_vertices) {
-        lt_vertex* v = P.vertices + rel * (unsigned long long)P.max_vertices + nv;
-        v->point[0] = (double)px; v->point[1] = (double)py; v->point[2] = (double)pz;
-        v->direction[0] = (double)ux; v->direction[1] = (double)uy; v->direction[2] = (double)uz;
-        v->g_norm[0] = (double)gx; v->g_norm[1] = (double)gy; v->g_norm[2] = (double)gz;
-        v->throughput = (double)w; v->pdf_pos = (double)pdf_pos; v->pdf_dir = (double)pdf_dir;
-        v->kind = kind; v->medium = medium; v->step = step; v->pad_ = 0;
-        nv++;
-        P.vertex_counts[rel] = nv;
-    }
-}
-
-// One deposit record per lane (or none) leaves the lane's run-length accumulator.  Atomic mode: a no-return
-// global atomic.  Log mode: the wave's records are compacted by ballot rank and appended, coalesced, to the wave's
-// current log chunk (SoA: voxel index, value); a chunk is claimed with one returning atomic per kLogChunk records.
-// If the log is exhausted the wave falls back to atomics, so a too-small log costs speed, never correctness.
-// A lane without a record passes idx == kNoVoxel (its val is then not read).  IDX_MASK (the slab walks): the wave's mask of
-// records is the ballot of that integer compare, taken in front of the tally-mode branch: there it IS the compare's result (one
-// v_cmp into a scalar pair).  Taken from the bool behind the branch (the mesh walks, which have no scalar pair to carry it in) it
-// costs a round trip through a VGPR (v_cndmask 0,1 + v_cmp_ne) in every wave-step.
-constexpr unsigned kLogExhausted = 0xfffffffeu;   // lg_chunk: this wave has found the log full (0xffffffff: no chunk claimed yet)
-constexpr unsigned kNoVoxel = 0xffffffffu;        // idx: no record
-template <int TALLY, bool IDX_MASK>
-LT_DEV void emit_deposit(const WalkParams& P, unsigned idx, typename TallyT<TALLY>::type val,
-                         unsigned& lg_cur, unsigned& lg_end, unsigned& lg_chunk, uint32_t* s_hist)
-{
-    typedef typename TallyT<TALLY>::type TV;
-    const bool has = idx != kNoVoxel;
-    unsigned long long m = 0;
-    if constexpr (IDX_MASK) m = __ballot(has);
-    if (P.log_idx == nullptr) {
-        if (has) tally_add<TALLY>(P.grid, idx, val);
-        return;
-    }
-    if constexpr (!IDX_MASK) m = __ballot(has);
-    if (m == 0ull) return;
-    const unsigned cnt = (unsigned)__popcll(m);
-    // (a wave that has found the log exhausted does not ask again: lg_chunk == kLogExhausted is sticky, so an undersized log
-    // costs each wave ONE extra returning atomic, not one per emit on 16 shared addresses, and the group counters stay
-    // within cap + resident waves -- far from wrapping grp + kLogGroups * c)
-    if (lg_chunk != kLogExhausted && lg_end - lg_cur < cnt) {
-        const int lane = threadIdx.x & 63;
-        const unsigned grp = blockIdx.x & (kLogGroups - 1);
-        if (lg_chunk < kLogExhausted && lane == 0) P.log_fill[lg_chunk] = lg_cur - lg_chunk * kLogChunk;
-        unsigned c = 0;
-        if (lane == 0) c = __hip_atomic_fetch_add(P.log_next + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        c = grp + kLogGroups * __builtin_amdgcn_readfirstlane(c);     // the group's own chunks: see kLogGroups
-        if (c < P.log_cap_chunks) { lg_chunk = c; lg_cur = c * kLogChunk; lg_end = lg_cur + kLogChunk; }
-        else { lg_chunk = kLogExhausted; lg_cur = lg_end = 0; }
-    }
-    if (lg_chunk == kLogExhausted) {  // log exhausted: back to the linear voxel index and a global atomic
-        if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(P.log_overflow, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (has) {
-            // (the divisors pass through an empty asm so that the reciprocal set-up of these divisions stays in this rare
-            // branch: left visible as loop invariants it was hoisted in front of the walk's loop and parked in registers)
-            unsigned ntx = P.log_ntx, nty = P.log_nty;
-            asm volatile("" : "+s"(ntx), "+s"(nty));
-            const unsigned tile = idx >> kTileShift, tx = tile % ntx, ty = (tile / ntx) % nty,
-                           tz = tile / (ntx * nty);
-            const unsigned vx = (tx << kTileBX) | (idx & 31u), vy = (ty << kTileBY) | ((idx >> 5) & 31u),
-                           vz = (tz << kTileBZ) | ((idx >> 10) & 15u);
-            tally_add<TALLY>(P.grid, (vz * (unsigned)P.ny + vy) * (unsigned)P.nx + vx, val);
-        }
-        return;
-    }
-    if (has) {
-        const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        P.log_idx[lg_cur + rank] = idx;
-        reinterpret_cast<TV*>(P.log_val)[lg_cur + rank] = val;
-        atomicAdd(&s_hist[idx >> P.log_hist_shift], 1u);   // histogram of the first partition pass's bins, kept in LDS
-    }
-    lg_cur += cnt;
-}
-
-constexpr unsigned kPacket = 64;  // photon ids taken from the global queue per atomic
-#ifndef LT_REFILL_MIN
-#define LT_REFILL_MIN 4
-#endif
-constexpr unsigned kRefillMin = LT_REFILL_MIN;   // dead lanes a wave collects before it refills them
-#ifndef LT_QUERY_MIN
-#define LT_QUERY_MIN 8
-#endif
-// mesh walks: lanes a wave collects before it serves their surface queries.  16 was best while every query walked the
-// BVH (~1500 instructions per service); with the near-triangle lists (nearest_listed: ~2-4 triangle tests) a service is
-// cheap and waiting costs more: C4 f64 walk 37.3 ms at 16, 34.4 at 8, 34.5 at 4, 47.6 at 32 (profiles/r02d_c4_near_lists.log)
-constexpr unsigned kQueryMin = LT_QUERY_MIN;
-// ... and when the tables live in global memory (GEOM 2): there a service that has to walk the BVH for some lane is a
-// chain of dependent loads that costs the wave the same whether 2 lanes or 20 walk, so it pays to wait for many: on the
-// 5140-triangle sphere 8 / 16 / 24 / 32 / 48 / 56 / 64 lanes give 4.7 / 5.4 / 6.3 / 7.1 / 8.5 / 8.2 / 5.2e9
-// photon-steps/s f64 (profiles/r02e_large_mesh_query_threshold.log).  LT_QUERY_MIN in the environment overrides both.
-constexpr unsigned kQueryMinGlobal = 48;
-#ifndef LT_QUERY_MAX_AGE
-#define LT_QUERY_MAX_AGE 8
-#endif
-// ... but no lane waits longer than this many wave iterations: where queries are rare (a dense medium around a large mesh)
-// the lanes that wait would idle until enough of them have trickled in -- the 5140-triangle sphere in a medium of ten
-// times the scattering ran at 4.2e9 photon-steps/s without this bound and at 9.1-9.5e9 with 4 ... 10; C4 gains 1-5 % too
-// (profiles/r02e_large_mesh_query_threshold.log)
-constexpr unsigned kQueryMaxAge = LT_QUERY_MAX_AGE;
-#ifndef LT_MARCH_DRAIN_MIN
-#define LT_MARCH_DRAIN_MIN 8
-#endif
-// walk_kernel_m: queries whose march has ended and that only wait for their queued candidates to be tested; this many
-// trigger a drain of a queue that holds less than a full round (LT_QUERY_MIN in the environment overrides)
-constexpr unsigned kMarchDrainMin = LT_MARCH_DRAIN_MIN;
-
-// ---------------------------------------------------------------------------
-// the walk kernel
-// ---------------------------------------------------------------------------
-// minimum waves per SIMD the register allocator must leave room for (occupancy is what hides the latency of the
-// dependent f64 / transcendental chains once deposition no longer paces the walk)
-#ifndef LT_F64_WAVES
-#define LT_F64_WAVES 4        // f64 mesh walks: ~80 B of scratch per lane at 128 VGPRs, still 6 % faster than 3 waves (C4)
-#endif
-#ifndef LT_F64_GLOBAL_WAVES
-#define LT_F64_GLOBAL_WAVES 3 // f64 walks of meshes beyond LDS (grid march): the DDA state on top of the photon's does not fit 128 VGPRs
-#endif
-#ifndef LT_F64_SLAB_WAVES
-#define LT_F64_SLAB_WAVES 4   // f64 slab walks fit 128 VGPRs without scratch since the polynomial constants live in SGPRs
-#endif
-#ifndef LT_F32_WAVES
-#define LT_F32_WAVES 5
-#endif
-// where the walk keeps the grid's origin / inverse voxel size / dimensions (lt_walk_kernel.inc, LT_INV_MODE), chosen per kernel
-// from same-box A/B runs (profiles/r04c_ab_modes.log):
-//   slab kernels   1, pinned VGPRs: f64 127 VGPRs, the fewest VALU instructions (C2 walk 26.3 ms against 26.9 converted in
-//                  the kernel, 27.0 as scalar arguments, 27.2 from LDS) -- and the leaner builds (109-110 VGPRs) made the log
-//                  reduction beside a half-occupancy walk much slower (two lanes: 40.6-42.5 ms against 37.5-37.9)
-//   LDS-mesh       2, LDS: the Cornell kernel needs its 128 VGPRs for the photon and the held step; no scratch (60 B pinned),
-//                  C4 walk 28.4 ms against 31.7 pinned and 33.5 in round 3
-//   march kernel   2, LDS: teapot / cow / pumpkin 19.0 / 18.9 / 17.8e9 f64 steps/s against 17.8 / 17.6 / 16.9 as scalar arguments
-//                  (156 VGPRs without scratch, but the scalar file overflows into v_readlane restores) and 18.1 / 18.0 / 17.1
-//                  pinned (profiles/r04d_march_modes.log); 154 VGPRs + 36 B of scratch
-#ifndef LT_INV_MODE_SLAB
-#define LT_INV_MODE_SLAB 1
-#endif
-#ifndef LT_INV_MODE_MESH
-#define LT_INV_MODE_MESH 2
-#endif
-#ifndef LT_INV_MODE_MARCH
-#define LT_INV_MODE_MARCH 2
-#endif
-#define LT_INV_MODE LT_INV_MODE_SLAB
-#define LT_WALK_NAME walk_kernel
-#define LT_WALK_BATCH 0
-#include "lt_walk_kernel.inc"
-#undef LT_WALK_NAME
-#undef LT_WALK_BATCH
-#undef LT_INV_MODE
-#define LT_INV_MODE LT_INV_MODE_MESH
-#define LT_WALK_NAME walk_kernel_q
-#define LT_WALK_BATCH 1
-#include "lt_walk_kernel.inc"
-#undef LT_WALK_NAME
-#undef LT_WALK_BATCH
-#undef LT_INV_MODE
-#define LT_INV_MODE LT_INV_MODE_MARCH
-#define LT_WALK_NAME walk_kernel_m
-#define LT_WALK_BATCH 2
-#include "lt_walk_kernel.inc"
-#undef LT_WALK_NAME
-#undef LT_WALK_BATCH
-#undef LT_INV_MODE
-
-// ---------------------------------------------------------------------------
-// variant dispatch
-// ---------------------------------------------------------------------------
-typedef void (*WalkFn)(const WalkParams);
-
-// CAPTURE (light sub-path vertices, f4) is a compile-time variant: the capture code costs the plain walk registers
-// even behind a never-taken branch (36-84 B of scratch per lane, walk 29.7 -> 34.6 ms when it was a run-time test).
-// Captures run the f64 walk with the XORWOW generator.
-template <typename R, int GEOM, bool TABLE, bool CAPTURE>
-static WalkFn pick_tally(int tally)
-{
-    switch (tally) {
-    // slabs: walk_kernel; meshes: walk_kernel_q (the same body with batched BVH queries, lt_walk_kernel.inc)
-    case LT_TALLY_F32:
-        if constexpr (TABLE) return nullptr;
-        else if constexpr (GEOM == 0) return walk_kernel<R, GEOM, TABLE, LT_TALLY_F32, CAPTURE>;
-        else return walk_kernel_q<R, GEOM, TABLE, LT_TALLY_F32, CAPTURE>;
-    case LT_TALLY_F64:
-        if constexpr (GEOM == 0) return walk_kernel<R, GEOM, TABLE, LT_TALLY_F64, CAPTURE>;
-        else return walk_kernel_q<R, GEOM, TABLE, LT_TALLY_F64, CAPTURE>;
-    case LT_TALLY_U64FX:
-        if constexpr (GEOM == 0) return walk_kernel<R, GEOM, TABLE, LT_TALLY_U64FX, CAPTURE>;
-        else return walk_kernel_q<R, GEOM, TABLE, LT_TALLY_U64FX, CAPTURE>;
-    case LT_TALLY_NONE:
-        if constexpr (!TABLE && GEOM == 0 && !CAPTURE) return walk_kernel<R, GEOM, TABLE, LT_TALLY_NONE, false>; else return nullptr;
-    }
-    return nullptr;
-}
-
-// meshes beyond LDS with a march grid (Variant::mesh 3): walk_kernel_m, tables in global memory (GEOM 2)
-template <typename R, bool CAPTURE>
-static WalkFn pick_march(int tally)
-{
-    switch (tally) {
-    case LT_TALLY_F32: return walk_kernel_m<R, 2, false, LT_TALLY_F32, CAPTURE>;
-    case LT_TALLY_F64: return walk_kernel_m<R, 2, false, LT_TALLY_F64, CAPTURE>;
-    case LT_TALLY_U64FX: return walk_kernel_m<R, 2, false, LT_TALLY_U64FX, CAPTURE>;
-    }
-    return nullptr;
-}
-
-template <typename R, bool TABLE, bool CAPTURE>
-static WalkFn pick_geom(const Variant& v)
-{
-    if (v.mesh == 3) { if constexpr (!TABLE) return pick_march<R, CAPTURE>(v.tally); else return nullptr; }
-    if (v.mesh == 0) return pick_tally<R, 0, TABLE, CAPTURE>(v.tally);
-    if (v.mesh == 1) return pick_tally<R, 1, TABLE, CAPTURE>(v.tally);
-    if constexpr (!TABLE) return pick_tally<R, 2, TABLE, CAPTURE>(v.tally); else return nullptr;
-}
-
-// slab walks in two kernels (Variant::phase 1 / 2, lt_walk_kernel.inc "Tail split"): XORWOW, no capture
-template <typename R, int PHASE>
-static WalkFn pick_phase(int tally)
-{
-    switch (tally) {
-    case LT_TALLY_F32: return walk_kernel<R, 0, false, LT_TALLY_F32, false, PHASE>;
-    case LT_TALLY_F64: return walk_kernel<R, 0, false, LT_TALLY_F64, false, PHASE>;
-    case LT_TALLY_U64FX: return walk_kernel<R, 0, false, LT_TALLY_U64FX, false, PHASE>;
-    }
-    return nullptr;
-}
-
-// ... and the walk through a mesh in LDS (Variant::mesh 1)
-template <typename R, int PHASE>
-static WalkFn pick_phase_q(int tally)
-{
-    switch (tally) {
-    case LT_TALLY_F32: return walk_kernel_q<R, 1, false, LT_TALLY_F32, false, PHASE>;
-    case LT_TALLY_F64: return walk_kernel_q<R, 1, false, LT_TALLY_F64, false, PHASE>;
-    case LT_TALLY_U64FX: return walk_kernel_q<R, 1, false, LT_TALLY_U64FX, false, PHASE>;
-    }
-    return nullptr;
-}
-
-static WalkFn pick(const Variant& v)
-{
-    if (v.phase) {
-        if (v.mesh > 1 || v.table || v.capture) return nullptr;
-        if (v.mesh == 1) {
-            if (v.phase == 1) return v.f32 ? pick_phase_q<float, 1>(v.tally) : pick_phase_q<double, 1>(v.tally);
-            return v.f32 ? pick_phase_q<float, 2>(v.tally) : pick_phase_q<double, 2>(v.tally);
-        }
-        if (v.phase == 1) return v.f32 ? pick_phase<float, 1>(v.tally) : pick_phase<double, 1>(v.tally);
-        return v.f32 ? pick_phase<float, 2>(v.tally) : pick_phase<double, 2>(v.tally);
-    }
-    if (v.capture) return (v.f32 || v.table) ? nullptr : pick_geom<double, false, true>(v);
-    if (v.f32) return v.table ? nullptr : pick_geom<float, false, false>(v);
-    return v.table ? pick_geom<double, true, false>(v) : pick_geom<double, false, false>(v);
-}
-
-size_t walk_lds_bytes(const Variant& v, int n_media, int n_layers, int n_tris, int n_nodes, unsigned n_hist)
-{
-    if (v.mesh) n_layers = 0;
-    if (v.mesh != 1) { n_tris = 0; n_nodes = 0; }
-    // walk_kernel_m (mesh 3): the march's per-wave scratch (rays, best hits, candidate queue), four waves per workgroup.  The
-    // plain global-memory kernel (mesh 2: no march grid / LT_NO_MARCH) never touches it and keeps its LDS free
-    return v.f32 ? LdsLayout<float>(n_media, n_layers, n_tris, n_nodes, n_hist, v.mesh == 3 ? 4 * sizeof(MarchWave<float>) : 0).total
-                 : LdsLayout<double>(n_media, n_layers, n_tris, n_nodes, n_hist, v.mesh == 3 ? 4 * sizeof(MarchWave<double>) : 0).total;
-}
-
-int walk_max_blocks_per_cu(const Variant& v, int threads, size_t lds_bytes)
-{
-    WalkFn fn = pick(v);
-    if (!fn) return 0;
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(fn), threads, lds_bytes) != hipSuccess)
-        return 0;
-    return nb;
-}
-
-hipError_t launch_walk(const WalkParams& Pin, const Variant& v, const LaunchCfg& cfg, hipStream_t s)
-{
-    WalkFn fn = pick(v);
-    if (!fn) return hipErrorInvalidValue;
-    WalkParams P = Pin;
-    if (v.mesh) P.n_layers = 0; else { P.n_tris = 0; P.n_nodes = 0; }
-    if (cfg.lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfg.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(fn, dim3(cfg.blocks), dim3(cfg.threads), cfg.lds_bytes, s, P);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// query kernels: the same __device__ functions, one lane per query (f64)
-// ---------------------------------------------------------------------------
-__global__ void k_intersect_rays(const TriD<double>* tris, const NodeD<double>* nodes, int n_tris, int n_nodes,
-                                 const double* o, const double* d, const double* tmax, size_t n, int use_bvh,
-                                 const MarchGrid G, const int16_t* links, int32_t* prim, double* t)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (use_bvh == 2) {     // the walk's wave-cooperative march (256 threads per workgroup: four waves)
-        __shared__ MarchWave<double> mw[4];
-        const bool want = i < n;
-        const size_t k = want ? i : 0;
-        int pi; double tt;
-        march_service<double>(tris, nodes, n_nodes, G, &mw[threadIdx.x >> 6], want, o[3 * k], o[3 * k + 1], o[3 * k + 2], d[3 * k], d[3 * k + 1],
-                              d[3 * k + 2], tmax ? tmax[k] : __builtin_huge_val(), 0.0, pi, tt);
-        if (want) { prim[i] = pi; t[i] = tt; }
-        return;
-    }
-    if (i >= n) return;
-    double oo[3] = {o[3 * i], o[3 * i + 1], o[3 * i + 2]}, dd[3] = {d[3 * i], d[3 * i + 1], d[3 * i + 2]};
-    double tm = tmax ? tmax[i] : __builtin_huge_val();
-    int pi; double tt;
-    if (use_bvh == 4) nearest_bvh_ordered(tris, nodes, n_nodes, links + ray_octant(dd) * 2 * n_nodes, oo, dd, tm, pi, tt);   // front to back (the renderers' order)
-    else if (use_bvh == 3) nearest_march(tris, nodes, n_nodes, G, oo, dd, tm, 0.0, pi, tt);      // the same march, lane by lane
-    else if (use_bvh) nearest_bvh(tris, nodes, n_nodes, oo, dd, tm, pi, tt);
-    else nearest_brute(tris, n_tris, oo, dd, tm, pi, tt);
-    prim[i] = pi; t[i] = tt;
-}
-
-__global__ void k_triangle_intersect(const double* o, const double* d, const double* tris, size_t n, double* t)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    // derive the PreComputedTriangle fields exactly as the host does
-    // (S/primitives.py:105-111), without fused multiply-adds
-    const double* a = tris + 9 * i; const double* b = a + 3; const double* c = a + 6;
-    TriD<double> T;
-    {
-#pragma clang fp contract(off)
-        for (int k = 0; k < 3; k++) { T.a[k] = a[k]; T.ab[k] = b[k] - a[k]; T.ac[k] = c[k] - a[k]; }
-        double nn[3];
-        nn[0] = T.ab[1] * T.ac[2] - T.ab[2] * T.ac[1];
-        nn[1] = T.ab[2] * T.ac[0] - T.ab[0] * T.ac[2];
-        nn[2] = T.ab[0] * T.ac[1] - T.ab[1] * T.ac[0];
-        double l = ::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);
-        for (int k = 0; k < 3; k++) T.n[k] = nn[k] / l;
-    }
-    T.med_front = T.med_back = -1;
-    double oo[3] = {o[3 * i], o[3 * i + 1], o[3 * i + 2]}, dd[3] = {d[3 * i], d[3 * i + 1], d[3 * i + 2]};
-    t[i] = tri_hit(oo, dd, &T);
-}
-
-__global__ void k_intersect_bounds(const double* o, const double* d, const double* tmax, const double* boxes,
-                                   size_t n, int32_t* hit)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double oo[3] = {o[3 * i], o[3 * i + 1], o[3 * i + 2]};
-    double inv[3] = {1.0 / d[3 * i], 1.0 / d[3 * i + 1], 1.0 / d[3 * i + 2]};
-    double lo[3] = {boxes[6 * i], boxes[6 * i + 1], boxes[6 * i + 2]};
-    double hi[3] = {boxes[6 * i + 3], boxes[6 * i + 4], boxes[6 * i + 5]};
-    hit[i] = box_hit(lo, hi, oo, inv, tmax ? tmax[i] : __builtin_huge_val()) ? 1 : 0;
-}
-
-__global__ void k_eval(int fn, const double* in, size_t n, double* out)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    switch (fn) {
-    case LT_FN_HG_PDF: out[i] = hg_pdf(in[2 * i], in[2 * i + 1]); break;
-    case LT_FN_HG_SAMPLE: {
-        double g = in[2 * i + 1];
-        out[i] = hg_sample(in[2 * i], g, 1.0 - g * g, 1.0 + g * g, 1.0 / (2.0 * g));
-    } break;
-    case LT_FN_ONB: {
-        double nn[3] = {in[3 * i], in[3 * i + 1], in[3 * i + 2]}, v2[3], v3[3];
-        onb(nn, v2, v3);
-        for (int k = 0; k < 3; k++) { out[6 * i + k] = v2[k]; out[6 * i + 3 + k] = v3[k]; }
-    } break;
-    case LT_FN_DISK: { double dd[2]; disk(in[2 * i], in[2 * i + 1], dd); out[2 * i] = dd[0]; out[2 * i + 1] = dd[1]; } break;
-    case LT_FN_COSINE_HEMI: {
-        double nn[3] = {in[8 * i], in[8 * i + 1], in[8 * i + 2]}, wi[3] = {in[8 * i + 3], in[8 * i + 4], in[8 * i + 5]}, o4[4];
-        cosine_hemi(nn, wi, in[8 * i + 6], in[8 * i + 7], o4);
-        for (int k = 0; k < 4; k++) out[4 * i + k] = o4[k];
-    } break;
-    case LT_FN_REFLECT: {
-        double v[3] = {in[6 * i], in[6 * i + 1], in[6 * i + 2]}, nn[3] = {in[6 * i + 3], in[6 * i + 4], in[6 * i + 5]}, r[3];
-        reflect(v, nn, r);
-        for (int k = 0; k < 3; k++) out[3 * i + k] = r[k];
-    } break;
-    case LT_FN_BOUNDARY: {
-        double dd[3] = {in[8 * i], in[8 * i + 1], in[8 * i + 2]}, nf[3] = {in[8 * i + 3], in[8 * i + 4], in[8 * i + 5]}, ct, refr[3];
-        out[5 * i] = boundary(dd, nf, in[8 * i + 6], in[8 * i + 7], &ct, refr);
-        out[5 * i + 1] = ct; out[5 * i + 2] = refr[0]; out[5 * i + 3] = refr[1]; out[5 * i + 4] = refr[2];
-    } break;
-    case LT_FN_SPIN: {
-        double u[3] = {in[5 * i], in[5 * i + 1], in[5 * i + 2]};
-        spin<double, true>(u, in[5 * i + 3], in[5 * i + 4], kWalkMathTab);
-        for (int k = 0; k < 3; k++) out[3 * i + k] = u[k];
-    } break;
-    case LT_FN_WALK_MATH: {   // the walk's lean f64 primitives: -ln x, sin/cos(2 pi x), sqrt x, 1 / (1 + x)
-        const double x = in[i];
-        out[5 * i] = neg_log_tab(x, kWalkMathTab);
-        sincos_turn_tab(x, kWalkMathTab, &out[5 * i + 1], &out[5 * i + 2]);
-        out[5 * i + 3] = sqrt01(x);
-        out[5 * i + 4] = fast_div(1.0, 1.0 + x);
-    } break;
-    case LT_FN_WALK_MATH_RAW: {   // ... and the forms the f64 XORWOW walk applies to the raw draw
-        const unsigned k = (unsigned)in[i];
-        out[3 * i] = neg_log_raw(k, kWalkMathTab);
-        sincos_turn_raw(k, kWalkMathTab, &out[3 * i + 1], &out[3 * i + 2]);
-    } break;
-    }
-}
-
-__global__ void k_rng_raw(unsigned long long seed, unsigned long long photon_id, unsigned count, uint32_t* out)
-{
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    rocrand_state_xorwow st;
-    photon_stream(seed, photon_id, &st);
-    for (unsigned i = 0; i < count; i++) out[i] = rocrand(&st);
-}
-
-__global__ void k_grid_to_f64(const void* grid, int tally, size_t n, double* out)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        if (tally == LT_TALLY_F32) out[i] = (double)reinterpret_cast<const float*>(grid)[i];
-        else if (tally == LT_TALLY_F64) out[i] = reinterpret_cast<const double*>(grid)[i];
-        else out[i] = (double)reinterpret_cast<const unsigned long long*>(grid)[i] * (1.0 / LT_FX_SCALE);
-    }
-}
-
-// dst += src over whole grids, 16 bytes per lane (the grids are hipMalloc'ed: 256-byte aligned).  Joins the private
-// grid of an overlapped launch's second lane into the ctx grid: HBM-bound, 3 x grid bytes.
-template <typename T>
-__global__ void __launch_bounds__(256) k_grid_add(T* __restrict__ dst, const T* __restrict__ src, size_t n)
-{
-    constexpr size_t kV = 16 / sizeof(T);
-    struct alignas(16) V { T v[kV]; };
-    const size_t nv = n / kV;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
-        V a = reinterpret_cast<V*>(dst)[i];
-        const V b = reinterpret_cast<const V*>(src)[i];
-#pragma unroll
-        for (size_t k = 0; k < kV; k++) a.v[k] += b.v[k];
-        reinterpret_cast<V*>(dst)[i] = a;
-    }
-    for (size_t i = nv * kV + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] += src[i];
-}
-
-// ---------------------------------------------------------------------------
-// clearance grid builder: per cell, min over triangles of the distance from the cell centre to the triangle
-// (closest-point-on-triangle by regions), minus the half diagonal of the cell, shrunk by a safety margin
-// ---------------------------------------------------------------------------
-LT_DEV double point_tri_dist2(const double* p, const TriD<double>& T)
-{
-    const double ab[3] = {T.ab[0], T.ab[1], T.ab[2]}, ac[3] = {T.ac[0], T.ac[1], T.ac[2]};
-    const double ap[3] = {p[0] - T.a[0], p[1] - T.a[1], p[2] - T.a[2]};
-    const double d1 = dot3(ab, ap), d2 = dot3(ac, ap);
-    double q[3];
-    if (d1 <= 0 && d2 <= 0) { q[0] = 0; q[1] = 0; q[2] = 0; }                       // vertex A
-    else {
-        const double bp[3] = {ap[0] - ab[0], ap[1] - ab[1], ap[2] - ab[2]};
-        const double d3 = dot3(ab, bp), d4 = dot3(ac, bp);
-        const double cp[3] = {ap[0] - ac[0], ap[1] - ac[1], ap[2] - ac[2]};
-        const double d5 = dot3(ab, cp), d6 = dot3(ac, cp);
-        const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-        if (d3 >= 0 && d4 <= d3) { q[0] = ab[0]; q[1] = ab[1]; q[2] = ab[2]; }   // vertex B
-        else if (vc <= 0 && d1 >= 0 && d3 <= 0) { const double v = d1 / (d1 - d3); for (int k = 0; k < 3; k++) q[k] = v * ab[k]; }
-        else if (d6 >= 0 && d5 <= d6) { q[0] = ac[0]; q[1] = ac[1]; q[2] = ac[2]; }  // vertex C
-        else if (vb <= 0 && d2 >= 0 && d6 <= 0) { const double w = d2 / (d2 - d6); for (int k = 0; k < 3; k++) q[k] = w * ac[k]; }
-        else if (va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0) {
-            const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-            for (int k = 0; k < 3; k++) q[k] = ab[k] + w * (ac[k] - ab[k]);
-        } else {
-            const double den = 1.0 / (va + vb + vc), v = vb * den, w = vc * den;
-            for (int k = 0; k < 3; k++) q[k] = v * ab[k] + w * ac[k];
-        }
-    }
-    const double e[3] = {ap[0] - q[0], ap[1] - q[1], ap[2] - q[2]};
-    return dot3(e, e);
-}
-
-// f16 <-> f32 for the clearance records (values >= 0; encode rounds toward zero so that the bound stays conservative)
-LT_DEV unsigned half_down(double c)
-{
-    if (!(c > 0)) return 0u;
-    if (!(c < 65504.0)) return c == __builtin_huge_val() ? 0x7c00u : 0x7bffu;
-    _Float16 h = (_Float16)(float)c;
-    unsigned short b = __builtin_bit_cast(unsigned short, h);
-    if ((double)(float)h > c && b > 0) b--;
-    return b;
-}
-LT_DEV float half_up(unsigned bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(bits & 0xffffu)); }
-
-__global__ void k_build_clearance(const TriD<double>* tris, int n_tris, int near_lists, uint4* clear, int nx, int ny, int nz,
-                                  double ox, double oy, double oz, double hx, double hy, double hz)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)nx * ny * nz) return;
-    const int ix = (int)(i % nx), iy = (int)((i / nx) % ny), iz = (int)(i / ((size_t)nx * ny));
-    const double p[3] = {ox + (ix + 0.5) * hx, oy + (iy + 0.5) * hy, oz + (iz + 0.5) * hz};
-    // the five nearest triangles of the cell centre, nearest first (squared distances; ties keep the lower index first)
-    const double inf = __builtin_huge_val();
-    double best[5] = {inf, inf, inf, inf, inf};
-    int id[5] = {-1, -1, -1, -1, -1};
-    for (int t = 0; t < n_tris; t++) {
-        double d2 = point_tri_dist2(p, tris[t]);
-        int ti = t;
-#pragma unroll
-        for (int k = 0; k < 5; k++)
-            if (d2 < best[k]) { const double sd = best[k]; const int si = id[k]; best[k] = d2; id[k] = ti; d2 = sd; ti = si; }
-    }
-    const double half_diag = 0.5 * ::sqrt(hx * hx + hy * hy + hz * hz);
-    auto bound = [&](double d2) -> double {     // strictly conservative for every point of the cell
-        if (d2 == inf) return inf;
-        const double c = (::sqrt(d2) - half_diag) * (1.0 - 1e-6) - 1e-7 * (hx + hy + hz);
-        return c > 0 ? c : 0.0;
-    };
-    const double c0 = bound(best[0]);
-    float f = (float)c0;
-    if ((double)f > c0 && f > 0) f = __uint_as_float(__float_as_uint(f) - 1u);      // round toward zero
-    if (c0 == inf) f = 3.0e38f;
-    unsigned y = 0, z = 0xffffffffu, w = 0xffffffffu;
-    if (near_lists) {      // (ids are 16 bits: the host builds these records only for meshes whose tables fit LDS, <= ~1100 triangles, and refuses otherwise)
-        y = half_down(bound(best[2])) | (half_down(bound(best[4])) << 16);
-        z = (unsigned)(id[0] & 0xffff) | ((unsigned)(id[1] & 0xffff) << 16);      // (-1 & 0xffff = 0xffff: none)
-        w = (unsigned)(id[2] & 0xffff) | ((unsigned)(id[3] & 0xffff) << 16);
-    }
-    clear[i] = make_uint4(__float_as_uint(f), y, z, w);
-}
-
-hipError_t launch_build_clearance(const void* tris_f64, int n_tris, int near_lists, void* clear_records, int nx, int ny, int nz,
-                                  const double org[3], const double cell[3], hipStream_t s)
-{
-    const size_t n = (size_t)nx * ny * nz;
-    if (n == 0 || n_tris <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_build_clearance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                       reinterpret_cast<const TriD<double>*>(tris_f64), n_tris, near_lists, reinterpret_cast<uint4*>(clear_records), nx, ny, nz,
-                       org[0], org[1], org[2], cell[0], cell[1], cell[2]);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// march grid: c0 of every cell from the EXACT distance of the cell centre to the mesh, found by a nearest-point query in
-// the BVH (a subtree is skipped when its box is not nearer than the best triangle so far).  Two levels: a coarse grid
-// (cells 8 x 8 x 8 fine cells wide) is searched without a bound; a fine cell then starts from the bound its coarse cell
-// implies, dist(p) <= dist(q) + |p - q|, so its search only opens the few subtrees around that sphere.  Cost ~ cells x
-// tens of nodes instead of cells x triangles (k_build_clearance): 10^4 triangles get 128^3 cells instead of 58^3.
-// ---------------------------------------------------------------------------
-LT_DEV double point_box_dist2(const double* p, const NodeD<double>& nd)
-{
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const double e = __builtin_fmax(__builtin_fmax(nd.lo[k] - p[k], p[k] - nd.hi[k]), 0.0);
-        s += e * e;
-    }
-    return s;
-}
-LT_DEV double mesh_dist2(const TriD<double>* tris, const NodeD<double>* nodes, int n_nodes, const double* p, double best)
-{
-    int cur = 0;
-    while (cur < n_nodes) {
-        const NodeD<double>& nd = nodes[cur];
-        if (point_box_dist2(p, nd) <= best) {
-            if (nd.n_prims > 0) {
-                for (int k = 0; k < nd.n_prims; k++) best = __builtin_fmin(best, point_tri_dist2(p, tris[nd.offset + k]));
-                cur = nd.skip;
-            } else cur++;
-        } else cur = nd.skip;
-    }
-    return best;
-}
-__global__ void k_march_coarse(const TriD<double>* tris, const NodeD<double>* nodes, int n_nodes, const MarchGrid G, int kx, int ky,
-                               int kz, double* coarse)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)kx * ky * kz) return;
-    const int ix = (int)(i % kx), iy = (int)((i / kx) % ky), iz = (int)(i / ((size_t)kx * ky));
-    const double p[3] = {G.org[0] + (ix + 0.5) * 8.0 * G.h[0], G.org[1] + (iy + 0.5) * 8.0 * G.h[1], G.org[2] + (iz + 0.5) * 8.0 * G.h[2]};
-    coarse[i] = ::sqrt(mesh_dist2(tris, nodes, n_nodes, p, __builtin_huge_val()));
-}
-__global__ void k_march_fine(const TriD<double>* tris, const NodeD<double>* nodes, int n_nodes, const MarchGrid G, int kx, int ky,
-                             const double* coarse, uint2* cells)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)G.nx * G.ny * G.nz) return;
-    const int ix = (int)(i % G.nx), iy = (int)((i / G.nx) % G.ny), iz = (int)(i / ((size_t)G.nx * G.ny));
-    const double p[3] = {G.org[0] + (ix + 0.5) * G.h[0], G.org[1] + (iy + 0.5) * G.h[1], G.org[2] + (iz + 0.5) * G.h[2]};
-    const int qx = ix >> 3, qy = iy >> 3, qz = iz >> 3;
-    const double q[3] = {G.org[0] + (qx + 0.5) * 8.0 * G.h[0], G.org[1] + (qy + 0.5) * 8.0 * G.h[1], G.org[2] + (qz + 0.5) * 8.0 * G.h[2]};
-    const double e[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
-    const double up = (coarse[((size_t)qz * ky + qy) * kx + qx] + ::sqrt(dot3(e, e))) * (1.0 + 1e-9);     // dist(p) <= this
-    const double d2 = mesh_dist2(tris, nodes, n_nodes, p, up * up);
-    const double half_diag = 0.5 * ::sqrt(G.h[0] * G.h[0] + G.h[1] * G.h[1] + G.h[2] * G.h[2]);
-    // strictly conservative for every point of the cell (as k_build_clearance)
-    double c0 = (::sqrt(d2) - half_diag) * (1.0 - 1e-6) - 1e-7 * (G.h[0] + G.h[1] + G.h[2]);
-    if (!(c0 > 0)) c0 = 0.0;
-    float f = (float)c0;
-    if ((double)f > c0 && f > 0) f = __uint_as_float(__float_as_uint(f) - 1u);      // round toward zero
-    cells[i].x = (__float_as_uint(f) & ~kMarchCountMask) | (cells[i].x & kMarchCountMask);      // the low bits hold the cell's candidate count
-}
-hipError_t launch_march_clearance(const void* tris_f64, const void* nodes_f64, int n_nodes, const MarchGrid& G, uint2* cells,
-                                  double* coarse, hipStream_t s)
-{
-    const size_t n = (size_t)G.nx * G.ny * G.nz;
-    if (n == 0 || n_nodes <= 0) return hipSuccess;
-    const int kx = (G.nx + 7) / 8, ky = (G.ny + 7) / 8, kz = (G.nz + 7) / 8;
-    const size_t nc = (size_t)kx * ky * kz;
-    hipLaunchKernelGGL(k_march_coarse, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const TriD<double>*>(tris_f64),
-                       reinterpret_cast<const NodeD<double>*>(nodes_f64), n_nodes, G, kx, ky, kz, coarse);
-    hipLaunchKernelGGL(k_march_fine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const TriD<double>*>(tris_f64),
-                       reinterpret_cast<const NodeD<double>*>(nodes_f64), n_nodes, G, kx, ky, coarse, cells);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// surface path tracer: trace_path + render_scene of S/path_tracing_fix1.py:18-169,
-// one lane per pixel, samples looped in the lane (no atomics: a pixel has one owner)
-// ---------------------------------------------------------------------------
-LT_DEV void mark_unused(double* rand_0, size_t base, int from, int D)  // :36-38, :64-66, :128-130
-{
-    for (int b = from; b < D; b++) rand_0[base + b] = __builtin_huge_val();
-}
-
-// cast_one_shadow_ray (S/light_samples.py:36-61): radiance * brdf * geometry term * area of light sample `choice`
-// as seen from X (offset along n); false when the sample is occluded.
-__device__ __forceinline__ bool shadow_direct(const RenderParams& P, const TriD<double>* tris, const NodeD<double>* nodes, const int16_t* links,
-                                              const double X[3], const double n[3], const lt_surface_material& M,
-                                              int choice, double out[3])
-{
-    const double eps = 1e-6, inv_pi = 0.3183098861837907, inf = __builtin_huge_val();
-    const double so[3] = {X[0] + eps * n[0], X[1] + eps * n[1], X[2] + eps * n[2]};
-    const lt_point_light lt = P.lights[choice];
-    double v[3] = {lt.source[0] - so[0], lt.source[1] - so[1], lt.source[2] - so[2]};
-    const double mag = ::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    const double sd[3] = {v[0] / mag, v[1] / mag, v[2] / mag};
-    // (the reference takes the nearest hit of the shadow ray and asks whether it lies at mag - EPSILON or beyond, :49-52: the
-    // sample is hidden exactly when SOME triangle is hit nearer than that, so the search stops at the first one it finds)
-    int sp; double st;
-    nearest_bvh_render(tris, nodes, P.n_nodes, links, so, sd, mag - eps, sp, st, true);
-    (void)inf;
-    if (sp >= 0) return false;
-    const double cos_t = dot3(n, sd);
-    const double nsd[3] = {-sd[0], -sd[1], -sd[2]};
-    const double cos_p = dot3(lt.normal, nsd);
-    const double geom = ::fabs(cos_t * cos_p) / (mag * mag);
-#pragma unroll
-    for (int k = 0; k < 3; k++) out[k] = (lt.radiance[k] * (M.diffuse[k] * inv_pi)) * geom * lt.total_area;
-    return true;
-}
-
-// cos x for |x| <= 1 + rounding (the reference takes the cosine of a DOT PRODUCT of unit vectors, quirk B5): Taylor series to
-// x^24 / 24!, truncation < 2e-26 -- OCML's general cos carries a Payne-Hanek reduction for huge arguments and its pow a log / exp pair with
-// double-double arithmetic; inlined into the render kernels they cost ~100 VGPRs for one Schlick term
-__device__ __forceinline__ double cos_unit(double x)
-{
-    const double z = x * x;
-    double p = 1.6117373109360196e-24;                     //  1/24!
-    p = __builtin_fma(p, z, -8.8967913924505741e-22);      // -1/22!
-    p = __builtin_fma(p, z, 4.1103176233121648e-19);       //  1/20!
-    p = __builtin_fma(p, z, -1.5619206968586225e-16);      // -1/18!
-    p = __builtin_fma(p, z, 4.7794773323873853e-14);       //  1/16!
-    p = __builtin_fma(p, z, -1.1470745597729725e-11);      // -1/14!
-    p = __builtin_fma(p, z, 2.0876756987868099e-09);       //  1/12!
-    p = __builtin_fma(p, z, -2.7557319223985891e-07);      // -1/10!
-    p = __builtin_fma(p, z, 2.4801587301587302e-05);       //  1/8!
-    p = __builtin_fma(p, z, -1.3888888888888889e-03);      // -1/6!
-    p = __builtin_fma(p, z, 4.1666666666666664e-02);       //  1/4!
-    p = __builtin_fma(p, z, -0.5);
-    return __builtin_fma(p, z, 1.0);
-}
-
-// mirror (:82-85) and glass (:86-119, kept as written, quirk B5) branches of trace_path: new ray in o, d
-__device__ __forceinline__ void specular_bounce(const lt_surface_material& M, const double X[3], const double n[3],
-                                                bool inside, double r0, double o[3], double d[3])
-{
-    const double eps = 1e-6;
-    if (!M.is_mirror) {
-        const double n1 = inside ? M.ior : 1.0, n2 = inside ? 1.0 : M.ior;
-        const double R0 = ((n1 - n2) / (n1 + n2)) * ((n1 - n2) / (n1 + n2));
-        const double theta = dot3(d, n);
-        // (theta is a dot product of unit vectors; x^5 by three products: within 2 ulp of pow(x, 5.0), the render's pins hold to 1e-9)
-        const double om = 1 - cos_unit(theta), om2 = om * om;
-        const double refl_prob = R0 + (1 - R0) * (om2 * om2 * om);
-        double Nr = M.ior;
-        if (theta > 0) Nr = 1 / Nr;
-        Nr = 1 / Nr;
-        const double cos_theta = -theta;
-        const double rad = 1 - (Nr * Nr) * (1 - cos_theta * cos_theta);
-        if (rad > 0 && r0 > refl_prob) {
-            const double kk = Nr * cos_theta - ::sqrt(rad);
-            double tr[3] = {d[0] * Nr + n[0] * kk, d[1] * Nr + n[1] * kk, d[2] * Nr + n[2] * kk};
-            normalize3(tr);
-#pragma unroll
-            for (int k = 0; k < 3; k++) { o[k] = X[k] - eps * n[k]; d[k] = tr[k]; }
-            return;
-        }
-    }
-    double r[3]; reflect(d, n, r);
-#pragma unroll
-    for (int k = 0; k < 3; k++) { o[k] = X[k] + eps * n[k]; d[k] = r[k]; }
-}
-
-
-// One lane per PATH (pixel, sample), 256 lanes per workgroup: a workgroup owns PPB = max(1, 256 / S) whole pixels, its lanes
-// trace their paths side by side, park the radiance in LDS, and one lane per pixel then adds its samples in ascending order --
-// the reference's own order of summation (:148-164), so the image is what the sample loop of round 1-3's kernel gave, bit for
-// bit.  (That kernel ran one lane per pixel over all its samples: 90 000 lanes for the notebook's 300 x 300 render, a third of
-// the device's lanes for 50 sequential paths each.)  Pixels with more than 256 samples take several rounds.  The scene tables
-// (triangles, BVH nodes, materials: 7 KB for the notebook's scene) are staged in LDS when they fit 48 KiB (LDS_TABLES) and
-// lt_set_tuning "render_lds_tables" is not 0; the 2000 point lights (160 KB) and the random tables stay in global memory.
-constexpr int kRenderThreads = 256;
-#ifndef LT_RENDER_WAVES
-#define LT_RENDER_WAVES 4      // waves per SIMD the register allocator leaves room for: 2 (172 VGPRs, no scratch) 7.1 ms, 3 (168 + 12 B)
-                               // 5.2 ms, 4 (128 + 188 B of scratch) 4.6 ms for the 300 x 300 x 50 spp render (profiles/r04e_render_time.log)
-#endif
-template <bool LDS_TABLES>
-__global__ void __launch_bounds__(kRenderThreads, LT_RENDER_WAVES) k_render_surface(const RenderParams P)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char r_lds[];
-    double* s_L = reinterpret_cast<double*>(r_lds);                                       // [256][3] radiance of the lanes' paths
-    const size_t off_t = (size_t)kRenderThreads * 3 * sizeof(double);
-    const size_t off_n = off_t + (size_t)P.n_tris * sizeof(TriD<double>), off_m = off_n + (size_t)P.n_nodes * sizeof(NodeD<double>);
-    const TriD<double>* tris = LDS_TABLES ? reinterpret_cast<const TriD<double>*>(r_lds + off_t) : reinterpret_cast<const TriD<double>*>(P.tris);
-    const NodeD<double>* nodes = LDS_TABLES ? reinterpret_cast<const NodeD<double>*>(r_lds + off_n) : reinterpret_cast<const NodeD<double>*>(P.nodes);
-    const lt_surface_material* mats = LDS_TABLES ? reinterpret_cast<const lt_surface_material*>(r_lds + off_m) : P.mats;
-    const size_t off_k = off_m + (size_t)P.n_tris * sizeof(lt_surface_material);
-    const int16_t* links = LDS_TABLES ? reinterpret_cast<const int16_t*>(r_lds + off_k) : P.links;
-    if constexpr (LDS_TABLES) {
-        lds_copy(r_lds + off_k, P.links, (size_t)((16 * P.n_nodes * 2 + 3) / 4) * 4);
-        lds_copy(r_lds + off_t, P.tris, (size_t)P.n_tris * sizeof(TriD<double>));
-        lds_copy(r_lds + off_n, P.nodes, (size_t)P.n_nodes * sizeof(NodeD<double>));
-        lds_copy(r_lds + off_m, P.mats, (size_t)P.n_tris * sizeof(lt_surface_material));
-        __syncthreads();
-    }
-    const double eps = 1e-6, inv_pi = 0.3183098861837907, inf = __builtin_huge_val();
-    const int tid = threadIdx.x;
-    const int chunk = P.S < kRenderThreads ? P.S : kRenderThreads;       // samples of one pixel traced per round
-    const int ppb = kRenderThreads / chunk;                              // whole pixels per workgroup
-    const int pl = tid / chunk, sl = tid % chunk;                        // this lane's pixel (local) and sample slot
-    const int pix = blockIdx.x * ppb + pl;
-    const bool owner = tid < ppb && blockIdx.x * ppb + tid < P.W * P.H;  // lane tid sums local pixel tid
-    double color[3] = {0, 0, 0};
-    for (int s0 = 0; s0 < P.S; s0 += chunk) {
-        const int smp = s0 + sl;
-        double L[3] = {0, 0, 0};
-        if (pl < ppb && pix < P.W * P.H && smp < P.S) {
-            const int i = pix / P.W, j = pix % P.W;
-            const size_t base = (((size_t)i * P.W + j) * P.S + smp) * (size_t)P.D;
-            // camera ray, :152-160 (anti-alias jitter re-uses the bounce-0 uniform for x and y)
-            double o[3] = {P.cam[0], P.cam[1], P.cam[2]};
-            const double jit = P.rand_0[base];
-            double d[3] = {P.xs[j] + jit / (double)P.W - o[0], P.ys[i] + jit / (double)P.H - o[1], P.f_distance - o[2]};
-            normalize3(d);
-            double thr[3] = {1, 1, 1};
-            // ONE traversal site serves both kinds of ray: (o, d) is the ray the next search follows -- the path's own ray, or,
-            // while `shadow`, the shadow ray of the diffuse hit (`hit`, `thit` on the stashed path ray po, pd) whose shading
-            // is completed when the search returns.  Two inlined copies of the traversal cost the kernel 221 VGPRs; the
-            // expressions evaluated are those of trace_path / cast_one_shadow_ray, in the same order.
-            bool shadow = false;
-            int hit = -1; double thit = 0, smag = 0;
-            double po[3] = {0, 0, 0}, pd[3] = {0, 0, 1};
-            for (int bounce = 0;;) {
-                if (!shadow && bounce >= P.D) break;                        // :24-26
-                int prim; double t;
-                nearest_bvh_render(tris, nodes, P.n_nodes, links, o, d, shadow ? smag - eps : inf, prim, t, shadow);    // hit_object, :32 / cast_one_shadow_ray
-                const double r0 = P.rand_0[base + bounce], r1 = P.rand_1[base + bounce];
-                if (!shadow) {
-                    if (prim < 0) { mark_unused(P.rand_0, base, bounce, P.D); break; }
-                    const lt_surface_material M = mats[prim];
-                    double n[3] = {tris[prim].n[0], tris[prim].n[1], tris[prim].n[2]};
-                    const double X[3] = {o[0] + t * d[0], o[1] + t * d[1], o[2] + t * d[2]};
-                    if (M.is_light) { L[0] += M.emission * thr[0]; L[1] += M.emission * thr[1]; L[2] += M.emission * thr[2]; }
-                    bool inside = false;
-                    if (dot3(n, d) > 0) { n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; inside = true; }   // :48-51
-                    if (M.is_diffuse) {
-                        // direct light: cast_one_shadow_ray, S/light_samples.py:36-61 -- the shadow ray becomes the ray to follow
-                        const lt_point_light lt = P.lights[P.light_choice[base + bounce]];
-#pragma unroll
-                        for (int k = 0; k < 3; k++) { po[k] = o[k]; pd[k] = d[k]; o[k] = X[k] + eps * n[k]; }
-                        double v[3] = {lt.source[0] - o[0], lt.source[1] - o[1], lt.source[2] - o[2]};
-                        smag = ::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-                        d[0] = v[0] / smag; d[1] = v[1] / smag; d[2] = v[2] / smag;
-                        hit = prim; thit = t; shadow = true;
-                        continue;
-                    } else if (M.is_mirror || M.transmission > 0.0) {           // :82-119
-                        specular_bounce(M, X, n, inside, r0, o, d);
-                    } else break;                                               // :121-123
-                } else {
-                    // the shadow ray is back: finish the diffuse hit it belongs to
-                    shadow = false;
-                    const lt_surface_material M = mats[hit];
-                    double n[3] = {tris[hit].n[0], tris[hit].n[1], tris[hit].n[2]};
-                    if (dot3(n, pd) > 0) { n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; }
-                    const double X[3] = {po[0] + thit * pd[0], po[1] + thit * pd[1], po[2] + thit * pd[2]};
-                    if (prim < 0) {      // nothing nearer than the light sample: radiance * brdf * geometry term * area, :53-61
-                        const lt_point_light lt = P.lights[P.light_choice[base + bounce]];
-                        const double cos_t = dot3(n, d);
-                        const double nsd[3] = {-d[0], -d[1], -d[2]};
-                        const double cos_p = dot3(lt.normal, nsd);
-                        const double geom = ::fabs(cos_t * cos_p) / (smag * smag);
-#pragma unroll
-                        for (int k = 0; k < 3; k++) L[k] += thr[k] * ((lt.radiance[k] * (M.diffuse[k] * inv_pi)) * geom * lt.total_area);
-                    }
-                    // indirect: cosine lobe, :63-80
-                    double o4[4];
-                    cosine_hemi<double, true>(n, pd, r0, r1, o4);
-                    if (o4[3] == 0) { mark_unused(P.rand_0, base, bounce + 1, P.D); break; }
-                    const double cos_theta = o4[0] * n[0] + o4[1] * n[1] + o4[2] * n[2];
-#pragma unroll
-                    for (int k = 0; k < 3; k++) {
-                        thr[k] *= (M.diffuse[k] * inv_pi) * cos_theta / o4[3];
-                        o[k] = X[k] + eps * o4[k];
-                        d[k] = o4[k];
-                    }
-                }
-                if (bounce > 5) {                                           // russian roulette, :126-132
-                    const double rr = ::fmax(0.05, 1 - thr[1]);
-                    if (r0 < rr) { mark_unused(P.rand_0, base, bounce + 1, P.D); break; }
-                    thr[0] /= 1 - rr; thr[1] /= 1 - rr; thr[2] /= 1 - rr;
-                }
-                bounce++;
-            }
-        }
-        s_L[tid * 3] = L[0]; s_L[tid * 3 + 1] = L[1]; s_L[tid * 3 + 2] = L[2];
-        __syncthreads();
-        if (owner) {        // color += light, sample by sample (:162)
-            const int ns = P.S - s0 < chunk ? P.S - s0 : chunk;
-            for (int q = 0; q < ns; q++) {
-                const double* l = s_L + (size_t)(tid * chunk + q) * 3;
-                color[0] += l[0]; color[1] += l[1]; color[2] += l[2];
-            }
-        }
-        __syncthreads();
-    }
-    if (owner) {
-        const size_t px = (size_t)blockIdx.x * ppb + tid;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {                                       // :164-166
-            double c = color[k] / (double)P.S;
-            c = c < 0 ? 0.0 : (c > 1 ? 1.0 : c);
-            P.image[px * 3 + k] += 0.25 * c;
-        }
-    }
-}
-
-// path_tracing_old.py:17-171 -- the recursive ancestor of trace_path that examples/LTS.ipynb still calls.  A diffuse hit
-// calls trace_path(ray, bounce + 1) on the SHARED ray and, once that returns, carries on from wherever the callee left
-// the ray (:68-80); emission counts at bounce 0 only (:45), the direct term is not throughput-weighted (:80), roulette
-// starts after bounce 3 (:127) and the pixel is overwritten with clip(mean) (:167).  The recursion is unrolled into an
-// explicit per-lane stack of (throughput, light, direct, r0, bounce) frames, visited in the reference's depth-first
-// order so that the +inf markers written into rand_0 are read back exactly where the reference reads them.
-// One lane per PATH (pixel, sample) as in k_render_surface, one wave per workgroup; the frame being executed lives in
-// registers, the frames of its callers in LDS ([depth][field][lane]: at most D of them, 45 KiB for the notebook's depth 8) --
-// rounds 1-3 kept the whole stack of 25 frames in scratch memory (2288 B per lane) and looped over a pixel's samples in one lane.
-constexpr int kOldThreads = 64, kOldFields = 11;      // thr[3], L[3], direct[3], r0, bounce
-__global__ void __launch_bounds__(kOldThreads) k_render_surface_old(const RenderParams P)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char r_lds[];
-    double* s_L = reinterpret_cast<double*>(r_lds);                       // [64][3]
-    double* s_st = s_L + kOldThreads * 3;                                 // [D][kOldFields][64]
-    const TriD<double>* tris = reinterpret_cast<const TriD<double>*>(P.tris);
-    const NodeD<double>* nodes = reinterpret_cast<const NodeD<double>*>(P.nodes);
-    const double eps = 1e-6, inv_pi = 0.3183098861837907, inf = __builtin_huge_val();
-    const int tid = threadIdx.x;
-    const int chunk = P.S < kOldThreads ? P.S : kOldThreads, ppb = kOldThreads / chunk;
-    const int pl = tid / chunk, sl = tid % chunk;
-    const int pix = blockIdx.x * ppb + pl;
-    const bool owner = tid < ppb && blockIdx.x * ppb + tid < P.W * P.H;
-    double color[3] = {0, 0, 0};
-    for (int s0 = 0; s0 < P.S; s0 += chunk) {
-        const int smp = s0 + sl;
-        double ret[3] = {0, 0, 0};
-        if (pl < ppb && pix < P.W * P.H && smp < P.S) {
-            const int i = pix / P.W, j = pix % P.W;
-            const size_t sample = ((size_t)i * P.W + j) * P.S + smp;
-            const size_t base = sample * (size_t)P.D;
-            const int32_t* choice = P.light_choice + sample * (size_t)P.choices;
-            unsigned n_shadow = 0;
-            double o[3] = {P.cam[0], P.cam[1], P.cam[2]};
-            const double jit = P.rand_0[base];                               // :158-159
-            double d[3] = {P.xs[j] + jit / (double)P.W - o[0], P.ys[i] + jit / (double)P.H - o[1], P.f_distance - o[2]};
-            normalize3(d);
-            int depth = 0;
-            bool resume = false;
-            // the frame in execution
-            double f_thr[3] = {1, 1, 1}, f_L[3] = {0, 0, 0}, f_direct[3] = {0, 0, 0}, f_r0 = 0.0;
-            int f_bounce = 0;
-            for (;;) {
-                bool done = false;
-                if (resume) {                                                // back from trace_path(bounce + 1), :78-80
-                    resume = false;
-#pragma unroll
-                    for (int k = 0; k < 3; k++) f_L[k] += (f_direct[k] + f_thr[k] * ret[k]);
-                } else if (f_bounce >= P.D) {                                // :24-25
-                    done = true;
-                } else {
-                    const double r0 = P.rand_0[base + f_bounce], r1 = P.rand_1[base + f_bounce];
-                    f_r0 = r0;
-                    int prim; double t;
-                    nearest_bvh_render(tris, nodes, P.n_nodes, P.links, o, d, inf, prim, t);
-                    if (prim < 0) { mark_unused(P.rand_0, base, f_bounce, P.D); done = true; }
-                    else {
-                        const lt_surface_material M = P.mats[prim];
-                        double n[3] = {tris[prim].n[0], tris[prim].n[1], tris[prim].n[2]};
-                        const double X[3] = {o[0] + t * d[0], o[1] + t * d[1], o[2] + t * d[2]};
-                        if (M.is_light && f_bounce == 0) {                   // :45-46
-#pragma unroll
-                            for (int k = 0; k < 3; k++) f_L[k] += M.emission * f_thr[k];
-                        }
-                        bool inside = false;
-                        if (dot3(n, d) > 0) { n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; inside = true; }
-                        if (M.is_diffuse) {
-                            if (!shadow_direct(P, tris, nodes, P.links, X, n, M, choice[n_shadow % (unsigned)P.choices], f_direct))
-                                f_direct[0] = f_direct[1] = f_direct[2] = 0;
-                            n_shadow++;
-                            double o4[4];
-                            cosine_hemi<double, true>(n, d, r0, r1, o4);
-                            if (o4[3] == 0) { mark_unused(P.rand_0, base, f_bounce + 1, P.D); done = true; }
-                            else {
-                                const double cos_theta = o4[0] * n[0] + o4[1] * n[1] + o4[2] * n[2];
-#pragma unroll
-                                for (int k = 0; k < 3; k++) {
-                                    f_thr[k] *= (M.diffuse[k] * inv_pi) * cos_theta / o4[3];
-                                    o[k] = X[k] + eps * o4[k];
-                                    d[k] = o4[k];
-                                }
-                                // trace_path(scene, ..., ray, bounce + 1, ...), :78 -- the caller's frame goes to LDS
-                                double* fr = s_st + ((size_t)depth * kOldFields) * kOldThreads + tid;
-#pragma unroll
-                                for (int k = 0; k < 3; k++) {
-                                    fr[(size_t)k * kOldThreads] = f_thr[k]; fr[(size_t)(3 + k) * kOldThreads] = f_L[k];
-                                    fr[(size_t)(6 + k) * kOldThreads] = f_direct[k];
-                                    f_thr[k] = 1; f_L[k] = 0; f_direct[k] = 0;
-                                }
-                                fr[(size_t)9 * kOldThreads] = f_r0; fr[(size_t)10 * kOldThreads] = (double)f_bounce;
-                                f_r0 = 0.0; f_bounce = f_bounce + 1;
-                                depth++;
-                                continue;
-                            }
-                        } else if (M.is_mirror || M.transmission > 0.0) {
-                            specular_bounce(M, X, n, inside, r0, o, d);
-                        } else done = true;                                  // :122-124
-                    }
-                }
-                if (!done && f_bounce > 3) {                                 // :127-133
-                    const double rr = ::fmax(0.05, 1 - f_thr[1]);
-                    if (f_r0 < rr) { mark_unused(P.rand_0, base, f_bounce + 1, P.D); done = true; }
-                    else { f_thr[0] /= 1 - rr; f_thr[1] /= 1 - rr; f_thr[2] /= 1 - rr; }
-                }
-                if (!done) { f_bounce++; continue; }
-                ret[0] = f_L[0]; ret[1] = f_L[1]; ret[2] = f_L[2];          // return light, :137
-                if (depth == 0) break;
-                depth--;                                                     // the caller's frame comes back
-                const double* fr = s_st + ((size_t)depth * kOldFields) * kOldThreads + tid;
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    f_thr[k] = fr[(size_t)k * kOldThreads]; f_L[k] = fr[(size_t)(3 + k) * kOldThreads];
-                    f_direct[k] = fr[(size_t)(6 + k) * kOldThreads];
-                }
-                f_r0 = fr[(size_t)9 * kOldThreads]; f_bounce = (int)fr[(size_t)10 * kOldThreads];
-                resume = true;
-            }
-        }
-        s_L[tid * 3] = ret[0]; s_L[tid * 3 + 1] = ret[1]; s_L[tid * 3 + 2] = ret[2];
-        __syncthreads();
-        if (owner) {        // color += light, sample by sample (:163)
-            const int ns = P.S - s0 < chunk ? P.S - s0 : chunk;
-            for (int q = 0; q < ns; q++) {
-                const double* l = s_L + (size_t)(tid * chunk + q) * 3;
-                color[0] += l[0]; color[1] += l[1]; color[2] += l[2];
-            }
-        }
-        __syncthreads();
-    }
-    if (owner) {
-        const size_t px = (size_t)blockIdx.x * ppb + tid;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {                                       // :166-167
-            double c = color[k] / (double)P.S;
-            c = c < 0 ? 0.0 : (c > 1 ? 1.0 : c);
-            P.image[px * 3 + k] = c;
-        }
-    }
-}
-
-hipError_t launch_render_surface(const RenderParams& P, hipStream_t s)
-{
-    const int n = P.W * P.H;
-    if (n <= 0) return hipSuccess;
-    if (P.variant == 1) {
-        const int chunk_o = P.S < kOldThreads ? P.S : kOldThreads, ppb_o = kOldThreads / chunk_o;
-        const size_t lds_o = ((size_t)kOldThreads * 3 + (size_t)P.D * kOldFields * kOldThreads) * sizeof(double);      // D <= kRenderOldMaxDepth: <= 137 KiB
-        if (lds_o > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_render_surface_old), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_o);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(k_render_surface_old, dim3((n + ppb_o - 1) / ppb_o), dim3(kOldThreads), lds_o, s, P);
-        return hipGetLastError();
-    }
-    const int chunk = P.S < kRenderThreads ? P.S : kRenderThreads, ppb = kRenderThreads / chunk;
-    const size_t tables = (size_t)P.n_tris * (sizeof(TriD<double>) + sizeof(lt_surface_material)) + (size_t)P.n_nodes * sizeof(NodeD<double>) +
-                          (size_t)((16 * P.n_nodes * 2 + 3) / 4) * 4;
-    const size_t lds_l = (size_t)kRenderThreads * 3 * sizeof(double);
-    // (a mesh without link tables has more than 32767 nodes, 3 MB of tables: never in LDS; the check keeps lds_copy off a null P.links)
-    if (tables <= 48 * 1024 && P.links && P.lds_tables != 0)
-        hipLaunchKernelGGL(k_render_surface<true>, dim3((n + ppb - 1) / ppb), dim3(kRenderThreads), lds_l + tables, s, P);
-    else
-        hipLaunchKernelGGL(k_render_surface<false>, dim3((n + ppb - 1) / ppb), dim3(kRenderThreads), lds_l, s, P);
-    return hipGetLastError();
-}
-
-static inline unsigned nblk(size_t n, unsigned t) { return (unsigned)((n + t - 1) / t); }
-
-hipError_t launch_intersect_rays(const void* tris, const void* nodes, int n_tris, int n_nodes, const double* o,
-                                 const double* d, const double* tmax, size_t n, int use_bvh, const MarchGrid* G, const int16_t* links,
-                                 int32_t* prim, double* t, hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    MarchGrid g;
-    if (use_bvh == 4 && !links) use_bvh = 1;
-    if (G) g = *G; else { memset(&g, 0, sizeof g); if (use_bvh == 2 || use_bvh == 3) use_bvh = 1; }
-    hipLaunchKernelGGL(k_intersect_rays, dim3(nblk(n, 256)), dim3(256), 0, s,
-                       reinterpret_cast<const TriD<double>*>(tris), reinterpret_cast<const NodeD<double>*>(nodes),
-                       n_tris, n_nodes, o, d, tmax, n, use_bvh, g, links, prim, t);
-    return hipGetLastError();
-}
-hipError_t launch_triangle_intersect(const double* o, const double* d, const double* tris, size_t n, double* t,
-                                     hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_triangle_intersect, dim3(nblk(n, 256)), dim3(256), 0, s, o, d, tris, n, t);
-    return hipGetLastError();
-}
-hipError_t launch_intersect_bounds(const double* o, const double* d, const double* tmax, const double* boxes,
-                                   size_t n, int32_t* hit, hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_intersect_bounds, dim3(nblk(n, 256)), dim3(256), 0, s, o, d, tmax, boxes, n, hit);
-    return hipGetLastError();
-}
-hipError_t launch_eval(int fn, const double* in, size_t n, double* out, hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_eval, dim3(nblk(n, 256)), dim3(256), 0, s, fn, in, n, out);
-    return hipGetLastError();
-}
-hipError_t launch_rng_raw(unsigned long long seed, unsigned long long photon_id, unsigned count, uint32_t* out,
-                          hipStream_t s)
-{
-    hipLaunchKernelGGL(k_rng_raw, dim3(1), dim3(64), 0, s, seed, photon_id, count, out);
-    return hipGetLastError();
-}
-hipError_t launch_grid_to_f64(const void* grid, int tally, size_t n, double* out, hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_grid_to_f64, dim3(2048), dim3(256), 0, s, grid, tally, n, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_grid_add(void* dst, const void* src, int tally, size_t n, hipStream_t s)
-{
-    if (tally == LT_TALLY_F32) hipLaunchKernelGGL(k_grid_add<float>, dim3(2048), dim3(256), 0, s, (float*)dst, (const float*)src, n);
-    else if (tally == LT_TALLY_F64) hipLaunchKernelGGL(k_grid_add<double>, dim3(2048), dim3(256), 0, s, (double*)dst, (const double*)src, n);
-    else hipLaunchKernelGGL(k_grid_add<unsigned long long>, dim3(2048), dim3(256), 0, s, (unsigned long long*)dst, (const unsigned long long*)src, n);
-    return hipGetLastError();
 }
 
 }  // namespace ltk

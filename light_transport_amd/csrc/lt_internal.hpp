@@ -1,5 +1,6 @@
-// lt_internal.hpp -- layouts shared by the host API (lt_api.cpp, g++) and the
-// gfx950 kernels (lt_kernels.hip, hipcc).  Not part of the public ABI.
+// lt_internal.hpp -- layouts and launcher declarations shared by the host API (lt_api.cpp, g++) and the gfx950 kernel
+// files (hipcc): lt_walk.hip, lt_query.hip, lt_render.hip (on the __device__ functions of lt_device.hpp) and lt_logtally.hip,
+// lt_tallysum.hip, lt_tallystats.hip (with lt_walk.hip on lt_tally.hpp); DESIGN.md section 1.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -208,12 +209,13 @@ struct LaunchCfg {
     size_t lds_bytes;
 };
 
+#define LT_TALLY_NONE 3  /* beside lt.h's LT_TALLY_*: diagnostic build of the walk without deposition (not part of the ABI) */
 // walk variants: precision x geometry x rng are compile-time, tally is too
 struct Variant {
     int f32;     // 0: f64 walk, 1: f32 walk
     int mesh;    // 0: layered slab, 1: mesh + BVH staged in LDS, 2: mesh + BVH read from global memory, 3: the same with a march grid (walk_kernel_m)
     int table;   // 0: XORWOW, 1: table RNG
-    int tally;   // LT_TALLY_*
+    int tally;   // LT_TALLY_* or LT_TALLY_NONE
     int capture; // 1: the build that stores light sub-path vertices (f64 walk, XORWOW)
     int phase;   // slab walks: 0 whole walk, 1 bulk (hands the last photons of every wave to a pool), 2 tail (walks the pool)
 };

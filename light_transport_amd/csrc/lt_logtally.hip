@@ -3,7 +3,7 @@
 // Why: with per-deposit global atomics the walk runs at the memory-side atomic unit's request rate
 // (~16e9 requests/s) while its arithmetic alone would sustain 4x that.  MI355X has 288 GB of
 // HBM at ~6 TB/s of streaming bandwidth, so the deposits are instead WRITTEN as a coalesced log
-// (lt_kernels.hip: emit_deposit) and reduced here with streaming passes only:
+// (lt_walk.hip: emit_deposit) and reduced here with streaming passes only:
 //   (walk)            records per partition bin, LDS histogram (<= 4 KiB per workgroup)
 //   k_log_scan_*      exclusive prefixes -> where every bin / tile's records will live, work-item tables
 //   k_log_part        counting sort of 4096-record work items by tile id in LDS; every digit's run leaves as one
@@ -22,19 +22,13 @@
 
 #include <atomic>
 
-#include "lt_internal.hpp"
+#include "lt_tally.hpp"
 
 namespace ltk {
 
 namespace {
 
-template <typename TV> __device__ __forceinline__ void lds_add(TV* p, TV v) { atomicAdd(p, v); }
-
-// type the LDS tile accumulates in: f32 deposits are summed in f64 (ds_add_f64 sustains twice the rate of
-// ds_add_f32 on the hot voxels here, and the f32 grid then sees one rounding per tile instead of one per deposit)
-template <typename TV> struct AccT { typedef TV type; };
-template <> struct AccT<float> { typedef double type; };
-
+// (the LDS tile accumulates in AccOf<TV>, lt_tally.hpp: f32 deposits are summed in f64)
 __device__ __forceinline__ unsigned tile_of(unsigned idx) { return idx >> kTileShift; }
 
 // four consecutive values: 32 bytes (two dwordx4 loads) for the 8-byte tallies, 16 bytes for f32
@@ -756,7 +750,7 @@ __global__ void __launch_bounds__(THREADS, LT_REDUCE_WAVES) k_log_reduce(LogRedu
 #if LT_RED_PRIO      // (compile option: the log reduction's waves issue ahead of a walk's -- they need 8 % of its VALU work and sit on the critical path of their job)
     __builtin_amdgcn_s_setprio(LT_RED_PRIO);
 #endif
-    typedef typename AccT<TV>::type AT;
+    typedef typename AccOf<TV>::type AT;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     AT* s_tile = reinterpret_cast<AT*>(s_raw);
     __shared__ uint32_t s_item[2][6];     // [tile, lo, hi, slices of the tile, item, hot] of the current and the next work item
@@ -899,9 +893,7 @@ template <typename TV, int PASS, bool HOT> static hipError_t launch_part_t(const
 }
 template <int PASS, bool HOT> static hipError_t launch_part(const LogReduceParams& L, hipStream_t s)
 {
-    if (L.tally == LT_TALLY_F32) return launch_part_t<float, PASS, HOT>(L, s);
-    if (L.tally == LT_TALLY_F64) return launch_part_t<double, PASS, HOT>(L, s);
-    return launch_part_t<unsigned long long, PASS, HOT>(L, s);
+    return with_tally_type(L.tally, [&](auto t) { return launch_part_t<decltype(t), PASS, HOT>(L, s); });
 }
 template <typename TV, int THREADS> static hipError_t launch_part_lds_t(const LogReduceParams& L, hipStream_t s)
 {
@@ -917,9 +909,7 @@ template <typename TV, int THREADS> static hipError_t launch_part_lds_t(const Lo
 }
 template <int THREADS> static hipError_t launch_part_lds(const LogReduceParams& L, hipStream_t s)
 {
-    if (L.tally == LT_TALLY_F32) return launch_part_lds_t<float, THREADS>(L, s);
-    if (L.tally == LT_TALLY_F64) return launch_part_lds_t<double, THREADS>(L, s);
-    return launch_part_lds_t<unsigned long long, THREADS>(L, s);
+    return with_tally_type(L.tally, [&](auto t) { return launch_part_lds_t<decltype(t), THREADS>(L, s); });
 }
 
 hipError_t launch_log_part1(const LogReduceParams& L, hipStream_t s)
@@ -962,7 +952,7 @@ hipError_t launch_log_part2(const LogReduceParams& L, hipStream_t s)
 
 template <typename TV, int THREADS> static hipError_t launch_reduce_t(const LogReduceParams& L, hipStream_t s)
 {
-    const size_t lds = (size_t)kTileSize * sizeof(typename AccT<TV>::type);
+    const size_t lds = (size_t)kTileSize * sizeof(typename AccOf<TV>::type);
     const void* fn = reinterpret_cast<const void*>(&k_log_reduce<TV, THREADS>);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -974,9 +964,7 @@ template <typename TV, int THREADS> static hipError_t launch_reduce_t(const LogR
 }
 template <int THREADS> static hipError_t launch_reduce_n(const LogReduceParams& L, hipStream_t s)
 {
-    if (L.tally == LT_TALLY_F32) return launch_reduce_t<float, THREADS>(L, s);
-    if (L.tally == LT_TALLY_F64) return launch_reduce_t<double, THREADS>(L, s);
-    return launch_reduce_t<unsigned long long, THREADS>(L, s);
+    return with_tally_type(L.tally, [&](auto t) { return launch_reduce_t<decltype(t), THREADS>(L, s); });
 }
 hipError_t launch_log_reduce(const LogReduceParams& L, hipStream_t s)
 {

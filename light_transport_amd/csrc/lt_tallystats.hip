@@ -10,17 +10,12 @@
 // IEEE double operation, so that a NumPy restatement gives the same bits.
 #include <hip/hip_runtime.h>
 
-#include "lt_internal.hpp"
+#include "lt_tally.hpp"
 
 #pragma clang fp contract(off)
 
 namespace ltk {
 namespace {
-
-typedef unsigned long long u64;
-
-template <typename T> struct AccOf { typedef double type; };
-template <> struct AccOf<u64> { typedef u64 type; };
 
 // 16 bytes of the grid: compared as two words, used as 16 / sizeof(T) elements
 template <typename T> union alignas(16) Bits16 { u64 q[2]; T v[16 / sizeof(T)]; };
@@ -31,16 +26,12 @@ template <int K> struct alignas(16) F64xK { double v[K]; };     // the m2 (or R)
 // workgroup in the fold.  Chunks of one piece measured 0.75 of the time of the same loads strided over the whole launch (512^3
 // grid, every voxel changed: 1100 -> 895 us): a chunk's reads and writes stay within a few DRAM pages.
 constexpr uint32_t kFoldDepth = 4;
-constexpr uint32_t kMaxBlocks = 2048;    // 256 CUs x 8 resident workgroups; the rest is grid-strided
 constexpr uint32_t kCopies = 32;         // k_stats_classes: copies of every LDS bin; a lane adds to copy (lane & 31)
 constexpr uint32_t kMaxClasses = kMaxStatEdges + 2;
 
 __device__ __forceinline__ double batch_diff(u64 g, u64 p) { return (double)(g - p) * (1.0 / LT_FX_SCALE); }
 __device__ __forceinline__ double batch_diff(double g, double p) { return g - p; }
 __device__ __forceinline__ double batch_diff(float g, float p) { return (double)g - (double)p; }
-__device__ __forceinline__ double as_weight(u64 v) { return (double)v * (1.0 / LT_FX_SCALE); }     // the units of lt_read_grid_f64
-__device__ __forceinline__ double as_weight(double v) { return v; }
-__device__ __forceinline__ double as_weight(float v) { return (double)v; }
 
 // Relative standard error of the mean over N equal batches (lt.h): S1 the voxel's weight, m2 its sum of squared batch
 // contributions.  One IEEE operation per line; both readouts go through here, so a voxel's class is the class of its R.
@@ -128,9 +119,6 @@ __global__ void __launch_bounds__(256) k_stats_relerr(const T* __restrict__ prev
 
 struct StatEdges { double e[kMaxStatEdges + 1]; };     // ascending, padded with NaN (never <= R) to 64
 
-__device__ __forceinline__ void lds_add(u64* p, u64 v) { atomicAdd(p, v); }
-__device__ __forceinline__ void lds_add(double* p, double v) { atomicAdd(p, v); }
-
 // Class of a voxel = number of edges <= R (0 .. n_edges), found by bisection of the edges in LDS; class n_cls - 1 collects the
 // voxels with S1 == 0 (no estimate).  part_cnt / part_w [workgroup][n_cls]: voxels and weight (u64 fixed point: the integer sum)
 // per class.  Most of a traced grid is empty and most of the rest falls in one or two classes, so one LDS bin per class would
@@ -206,38 +194,31 @@ __global__ void __launch_bounds__(256) k_stats_classes(const T* __restrict__ pre
     }
 }
 
-uint32_t blocks_for(size_t n_vox, size_t elem_bytes, uint32_t depth)
-{
-    const size_t per_block = (size_t)256 * depth * (16 / elem_bytes), b = (n_vox + per_block - 1) / per_block;
-    return (uint32_t)(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
-}
+// grid of a pass whose lanes each take `depth` 16-byte groups of voxels per round
+uint32_t stats_blocks(size_t n_vox, size_t elem_bytes, uint32_t depth) { return blocks_for(n_vox, (size_t)256 * depth * (16 / elem_bytes)); }
 
 }  // namespace
 
 hipError_t launch_stats_fold(const void* grid, void* prev, double* m2, int tally, size_t n, hipStream_t s)
 {
-    if (tally == LT_TALLY_F32)
-        hipLaunchKernelGGL(k_stats_fold<float>, dim3(blocks_for(n, 4, kFoldDepth)), dim3(256), 0, s, (const float*)grid, (float*)prev, m2, n);
-    else if (tally == LT_TALLY_F64)
-        hipLaunchKernelGGL(k_stats_fold<double>, dim3(blocks_for(n, 8, kFoldDepth)), dim3(256), 0, s, (const double*)grid, (double*)prev, m2, n);
-    else
-        hipLaunchKernelGGL(k_stats_fold<u64>, dim3(blocks_for(n, 8, kFoldDepth)), dim3(256), 0, s, (const u64*)grid, (u64*)prev, m2, n);
+    with_tally_type(tally, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_stats_fold<T>, dim3(stats_blocks(n, sizeof(T), kFoldDepth)), dim3(256), 0, s, (const T*)grid, (T*)prev, m2, n);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_stats_relerr(const void* prev, const double* m2, int tally, size_t n, uint64_t batches, double* out, hipStream_t s)
 {
     const double N = (double)batches;
-    if (tally == LT_TALLY_F32)
-        hipLaunchKernelGGL(k_stats_relerr<float>, dim3(blocks_for(n, 4, 4)), dim3(256), 0, s, (const float*)prev, m2, n, N, out);
-    else if (tally == LT_TALLY_F64)
-        hipLaunchKernelGGL(k_stats_relerr<double>, dim3(blocks_for(n, 8, 4)), dim3(256), 0, s, (const double*)prev, m2, n, N, out);
-    else
-        hipLaunchKernelGGL(k_stats_relerr<u64>, dim3(blocks_for(n, 8, 4)), dim3(256), 0, s, (const u64*)prev, m2, n, N, out);
+    with_tally_type(tally, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_stats_relerr<T>, dim3(stats_blocks(n, sizeof(T), 4)), dim3(256), 0, s, (const T*)prev, m2, n, N, out);
+    });
     return hipGetLastError();
 }
 
-uint32_t stats_summary_parts(size_t n_vox, int tally) { return blocks_for(n_vox, tally == LT_TALLY_F32 ? 4 : 8, kFoldDepth); }
+uint32_t stats_summary_parts(size_t n_vox, int tally) { return stats_blocks(n_vox, tally_elem_bytes(tally), kFoldDepth); }
 
 hipError_t launch_stats_summary(const void* prev, const double* m2, int tally, size_t n, uint64_t batches, const double* edges,
                                 int n_edges, void* partials, double* out, hipStream_t s)
@@ -249,12 +230,10 @@ hipError_t launch_stats_summary(const void* prev, const double* m2, int tally, s
     for (int i = 0; i <= kMaxStatEdges; i++) E.e[i] = i < n_edges ? edges[i] : __builtin_nan("");
     u64* part_cnt = (u64*)partials;
     void* part_w = part_cnt + (size_t)P * n_cls;
-    if (tally == LT_TALLY_F32)
-        hipLaunchKernelGGL(k_stats_classes<float>, dim3(P), dim3(256), 0, s, (const float*)prev, m2, n, N, E, n_cls, part_cnt, (double*)part_w);
-    else if (tally == LT_TALLY_F64)
-        hipLaunchKernelGGL(k_stats_classes<double>, dim3(P), dim3(256), 0, s, (const double*)prev, m2, n, N, E, n_cls, part_cnt, (double*)part_w);
-    else
-        hipLaunchKernelGGL(k_stats_classes<u64>, dim3(P), dim3(256), 0, s, (const u64*)prev, m2, n, N, E, n_cls, part_cnt, (u64*)part_w);
+    with_tally_type(tally, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_stats_classes<T>, dim3(P), dim3(256), 0, s, (const T*)prev, m2, n, N, E, n_cls, part_cnt, (typename AccOf<T>::type*)part_w);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     // out, n_cls 8-byte words each: weight (f64), raw weight (u64 fixed point only), voxels (u64), unused (the voxels as if they were fixed point)

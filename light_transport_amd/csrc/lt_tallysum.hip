@@ -1,5 +1,6 @@
-// lt_tallysum.hip -- sums of the voxel tally taken on the device (lt_tally_sum_axes, lt_tally_sum_columns): depth profiles,
-// projections, r-z maps.  Pure streaming reductions: every voxel is read once, and nothing but partial sums (some MiB where
+// lt_tallysum.hip -- every whole-grid pass over the voxel tally: the read-out as f64 (k_grid_to_f64), grid += grid
+// (k_grid_add), and the sums taken on the device (lt_tally_sum_axes, lt_tally_sum_columns): depth profiles, projections,
+// r-z maps.  The sums are pure streaming reductions: every voxel is read once, and nothing but partial sums (some MiB where
 // the output is small and the summed axis long; never a second grid) and the output is written.
 //
 // Everything is summed in an accumulator type A: u64 for the fixed-point tally (integer sums: exact, any order), f64 for the
@@ -13,17 +14,11 @@
 // integer tally, order-dependent in the last bits for float tallies.
 #include <hip/hip_runtime.h>
 
-#include "lt_internal.hpp"
+#include "lt_tally.hpp"
 
 namespace ltk {
 namespace {
 
-typedef unsigned long long u64;
-
-template <typename T> struct AccOf { typedef double type; };
-template <> struct AccOf<u64> { typedef u64 type; };
-
-template <typename T> struct alignas(16) Vec16 { T v[16 / sizeof(T)]; };           // an aligned 16-byte load
 template <typename T> struct alignas(sizeof(T)) VecEl { T v[16 / sizeof(T)]; };    // 16 bytes at element alignment (rows of odd length)
 
 constexpr uint32_t kRowPart = 4096;       // k_sum_rows: elements of a row that one wave sums
@@ -32,7 +27,6 @@ constexpr uint32_t kMinRows = 8;          //             ... or a part is down t
 constexpr uint32_t kBinPart = 2048;       // k_sum_bins: least voxels of a plane per workgroup (or four per bin, if that is more)
 constexpr uint32_t kBinGroups = 2048;     //             planes are split until this many workgroups have work
 constexpr uint32_t kFinishSerial = 32;    // k_sum_finish: up to this many parts one lane adds them, beyond it a wave does
-constexpr uint32_t kMaxBlocks = 2048;     // 256 CUs x 8 resident workgroups; the rest is grid-strided
 
 template <typename A>
 __device__ __forceinline__ A wave_sum(A v)      // fixed tree; lane 0 holds the total
@@ -116,9 +110,6 @@ __global__ void __launch_bounds__(256) k_sum_cols(const T* __restrict__ in, size
     }
 }
 
-__device__ __forceinline__ void lds_add(u64* p, u64 v) { atomicAdd(p, v); }
-__device__ __forceinline__ void lds_add(double* p, double v) { atomicAdd(p, v); }
-
 // grid: nz planes of `plane` voxels; bins[plane]: the bin of every (y, x) column, -1 = left out (the host has checked that
 // every entry is in -1 .. n_bins - 1).  partial[(pp * nz + z) * n_bins + bin] = what part pp of plane z adds to the bin.
 // One workgroup per (z, part): bins in LDS (8 bytes each: <= 32 KiB), zeroed, added to with LDS atomics, written out once.
@@ -169,8 +160,6 @@ __global__ void __launch_bounds__(256) k_sum_bins(const T* __restrict__ grid, co
     }
 }
 
-__device__ __forceinline__ double sum_as_weight(u64 v) { return (double)v * (1.0 / LT_FX_SCALE); }
-__device__ __forceinline__ double sum_as_weight(double v) { return v; }
 __device__ __forceinline__ void store_raw(u64* raw, size_t i, u64 v) { if (raw) raw[i] = v; }
 __device__ __forceinline__ void store_raw(u64*, size_t, double) {}
 
@@ -184,7 +173,7 @@ __global__ void __launch_bounds__(256) k_sum_finish(const A* __restrict__ partia
         for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_out; i += (size_t)gridDim.x * 256) {
             A acc = 0;
             for (uint32_t p = 0; p < P; p++) acc += partial[p * n_out + i];
-            out[i] = sum_as_weight(acc);
+            out[i] = as_weight(acc);
             store_raw(raw, i, acc);
         }
     } else {
@@ -194,17 +183,11 @@ __global__ void __launch_bounds__(256) k_sum_finish(const A* __restrict__ partia
             for (uint32_t p = lane; p < P; p += 64) acc += partial[p * n_out + i];
             acc = wave_sum(acc);
             if (lane == 0) {
-                out[i] = sum_as_weight(acc);
+                out[i] = as_weight(acc);
                 store_raw(raw, i, acc);
             }
         }
     }
-}
-
-uint32_t blocks_for(size_t n_items, size_t items_per_block)
-{
-    const size_t b = (n_items + items_per_block - 1) / items_per_block;
-    return (uint32_t)(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
 }
 
 struct RowPlan { size_t n_rows, L; uint32_t P; size_t elems() const { return n_rows * P; } };
@@ -299,9 +282,53 @@ void sum_bins_t(const T* grid, const int32_t* bins, const BinPlan& b, uint32_t n
 
 }  // namespace
 
+// the grid as f64 weights (lt_read_grid_f64)
+__global__ void k_grid_to_f64(const void* grid, int tally, size_t n, double* out)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        if (tally == LT_TALLY_F32) out[i] = as_weight(reinterpret_cast<const float*>(grid)[i]);
+        else if (tally == LT_TALLY_F64) out[i] = reinterpret_cast<const double*>(grid)[i];
+        else out[i] = as_weight(reinterpret_cast<const u64*>(grid)[i]);
+    }
+}
+
+// dst += src over whole grids, 16 bytes per lane (the grids are hipMalloc'ed: 256-byte aligned).  Joins the private
+// grid of an overlapped launch's second lane into the ctx grid: HBM-bound, 3 x grid bytes.
+template <typename T>
+__global__ void __launch_bounds__(256) k_grid_add(T* __restrict__ dst, const T* __restrict__ src, size_t n)
+{
+    constexpr size_t kV = 16 / sizeof(T);
+    typedef Vec16<T> V;
+    const size_t nv = n / kV;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
+        V a = reinterpret_cast<V*>(dst)[i];
+        const V b = reinterpret_cast<const V*>(src)[i];
+#pragma unroll
+        for (size_t k = 0; k < kV; k++) a.v[k] += b.v[k];
+        reinterpret_cast<V*>(dst)[i] = a;
+    }
+    for (size_t i = nv * kV + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] += src[i];
+}
+
+hipError_t launch_grid_to_f64(const void* grid, int tally, size_t n, double* out, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_grid_to_f64, dim3(kMaxBlocks), dim3(256), 0, s, grid, tally, n, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_grid_add(void* dst, const void* src, int tally, size_t n, hipStream_t s)
+{
+    with_tally_type(tally, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_grid_add<T>, dim3(kMaxBlocks), dim3(256), 0, s, (T*)dst, (const T*)src, n);
+    });
+    return hipGetLastError();
+}
+
 size_t tally_sum_axes_plan(int nx, int ny, int nz, int keep_mask, int tally, size_t* partial_bytes)
 {
-    const AxesPlan a = plan_axes((size_t)nx, (size_t)ny, (size_t)nz, keep_mask, tally == LT_TALLY_F32 ? 4 : 8);
+    const AxesPlan a = plan_axes((size_t)nx, (size_t)ny, (size_t)nz, keep_mask, tally_elem_bytes(tally));
     if (partial_bytes) *partial_bytes = ((a.rows ? a.rp.elems() : 0) + (a.cols ? a.cp.elems() : 0) + (a.rows2 ? a.rp2.elems() + 1 : 0)) * 8;
     return a.n_out;
 }
@@ -309,10 +336,8 @@ size_t tally_sum_axes_plan(int nx, int ny, int nz, int keep_mask, int tally, siz
 hipError_t launch_tally_sum_axes(const void* grid, int tally, int nx, int ny, int nz, int keep_mask, void* partials, double* out,
                                  unsigned long long* raw, hipStream_t s)
 {
-    const AxesPlan a = plan_axes((size_t)nx, (size_t)ny, (size_t)nz, keep_mask, tally == LT_TALLY_F32 ? 4 : 8);
-    if (tally == LT_TALLY_F32) sum_axes_t<float>((const float*)grid, a, partials, out, nullptr, s);
-    else if (tally == LT_TALLY_F64) sum_axes_t<double>((const double*)grid, a, partials, out, nullptr, s);
-    else sum_axes_t<u64>((const u64*)grid, a, partials, out, raw, s);
+    const AxesPlan a = plan_axes((size_t)nx, (size_t)ny, (size_t)nz, keep_mask, tally_elem_bytes(tally));
+    with_tally_type(tally, [&](auto t) { sum_axes_t((const decltype(t)*)grid, a, partials, out, raw, s); });
     return hipGetLastError();
 }
 
@@ -325,9 +350,7 @@ hipError_t launch_tally_sum_columns(const void* grid, int tally, int nx, int ny,
                                     double* out, unsigned long long* raw, hipStream_t s)
 {
     const BinPlan b = plan_bins((size_t)nx * (size_t)ny, (size_t)nz, (size_t)n_bins);
-    if (tally == LT_TALLY_F32) sum_bins_t<float>((const float*)grid, bins, b, (uint32_t)nz, (uint32_t)n_bins, partials, out, nullptr, s);
-    else if (tally == LT_TALLY_F64) sum_bins_t<double>((const double*)grid, bins, b, (uint32_t)nz, (uint32_t)n_bins, partials, out, nullptr, s);
-    else sum_bins_t<u64>((const u64*)grid, bins, b, (uint32_t)nz, (uint32_t)n_bins, partials, out, raw, s);
+    with_tally_type(tally, [&](auto t) { sum_bins_t((const decltype(t)*)grid, bins, b, (uint32_t)nz, (uint32_t)n_bins, partials, out, raw, s); });
     return hipGetLastError();
 }
 

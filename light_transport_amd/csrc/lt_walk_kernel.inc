@@ -1,4 +1,4 @@
-// lt_walk_kernel.inc -- body of the walk kernel, included twice by lt_kernels.hip:
+// lt_walk_kernel.inc -- body of the walk kernel, included three times by lt_walk.hip:
 //   LT_WALK_BATCH 0 -> walk_kernel     (layered slabs): prepare and complete a step back to back;
 //   LT_WALK_BATCH 1 -> walk_kernel_q   (meshes): lanes that need a BVH query hold their prepared step until enough
 //                                       of them have gathered (see the comment at the step).
