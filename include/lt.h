@@ -154,6 +154,7 @@ int lt_set_grid(lt_ctx* ctx, int nx, int ny, int nz, const double origin[3],
  * medium id the photon starts in (mesh scenes; ignored for layers). */
 int lt_set_source(lt_ctx* ctx, int type, const double pos[3], const double dir[3],
                   const double* extra, int start_medium);
+/* cap on a photon's steps: a photon alive after that many goes to w_capped with its weight (0: where it is emitted). */
 int lt_set_max_steps(lt_ctx* ctx, uint32_t max_steps);
 /* Experiment knobs -- tuning constants and diagnostic switches that tests and measurement tools vary; results do not
  * depend on any of them (the tests hold that down bit for bit).  value < 0 restores the built-in default.  Each knob is

@@ -1211,8 +1211,7 @@ int lt_set_source(lt_ctx* c, int type, const double pos[3], const double dir[3],
 int lt_set_max_steps(lt_ctx* c, uint32_t max_steps)
 {
     CHECK_CTX(c);
-    if (max_steps == 0) return c->fail(LT_E_INVALID, "lt_set_max_steps: must be > 0");
-    c->max_steps = max_steps;
+    c->max_steps = max_steps;      // (0: every photon is capped where it is emitted, with the weight that entered the scene)
     return LT_OK;
 }
 
@@ -1284,6 +1283,7 @@ int lt_launch(lt_ctx* c, uint64_t n_photons, uint64_t photon_offset, uint64_t se
     v.tally = c->tally;
     v.capture = c->max_vertices > 0 ? 1 : 0;
     v.phase = 0;
+    v.route = kRouteAtomic;      // (what the occupancy query below is asked about; launch_walk goes by P.log_idx)
     if (v.capture && (v.f32 || v.table)) return c->fail(LT_E_UNSUPPORTED, "lt_launch: vertex capture runs the f64 walk with the XORWOW generator");
     if (c->on(c->knob.diag_no_tally)) v.tally = LT_TALLY_NONE;  // diagnostic: time the walk without deposition
     if (v.table && v.f32) return c->fail(LT_E_UNSUPPORTED, "lt_launch: table RNG runs the f64 walk only");
@@ -1375,6 +1375,7 @@ int lt_launch(lt_ctx* c, uint64_t n_photons, uint64_t photon_offset, uint64_t se
     if (use_log) {
         LogRun R;
         R.c = c; R.P = P; R.v = v; R.cfg = cfg; R.G = G;
+        R.v.route = kRouteLog;      // (run_log_plan's occupancy query: the slab walk's log build)
         if (c->dmap_valid && (c->dmap_tiles != G.n_tiles || c->dmap_bits2 != G.bits2)) c->dmap_valid = c->tile_cnt_ready = false;   // (LT_LOG_BITS2 changed)
         c->stages_valid = false;
         for (LogLane& ln : c->lanes) ln.ev_used = 0;

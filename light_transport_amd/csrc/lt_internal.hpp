@@ -218,7 +218,11 @@ struct Variant {
     int tally;   // LT_TALLY_* or LT_TALLY_NONE
     int capture; // 1: the build that stores light sub-path vertices (f64 walk, XORWOW)
     int phase;   // slab walks: 0 whole walk, 1 bulk (hands the last photons of every wave to a pool), 2 tail (walks the pool)
+    int route;   // slab walks: kRouteAtomic / kRouteLog, a build each.  launch_walk sets it from WalkParams::log_idx, whatever it is
+                 // given; a caller sets it for walk_max_blocks_per_cu alone.  (The mesh walks test log_idx themselves.)
 };
+constexpr int kRouteAtomic = 0;   // deposit records go to the grid as global atomics
+constexpr int kRouteLog = 1;      // ... into the deposit log
 
 hipError_t launch_walk(const WalkParams& P, const Variant& v, const LaunchCfg& cfg, hipStream_t s);
 size_t walk_lds_bytes(const Variant& v, int n_media, int n_layers, int n_tris, int n_nodes, unsigned n_hist = 0);

@@ -120,59 +120,55 @@ LT_DEV void record_vertex(const WalkParams& P, unsigned long long rel, unsigned&
     }
 }
 
-// One deposit record per lane (or none) leaves the lane's run-length accumulator.  Atomic mode: a no-return
-// global atomic.  Log mode: the wave's records are compacted by ballot rank and appended, coalesced, to the wave's
+// One deposit record per lane (or none) leaves the lane's run-length accumulator.  Atomic route: a no-return
+// global atomic.  Log route: the wave's records are compacted by ballot rank and appended, coalesced, to the wave's
 // current log chunk (SoA: voxel index, value); a chunk is claimed with one returning atomic per kLogChunk records.
 // If the log is exhausted the wave falls back to atomics, so a too-small log costs speed, never correctness.
-// A lane without a record passes idx == kNoVoxel (its val is then not read).  IDX_MASK (the slab walks): the wave's mask of
-// records is the ballot of that integer compare, taken in front of the tally-mode branch: there it IS the compare's result (one
-// v_cmp into a scalar pair).  Taken from the bool behind the branch (the mesh walks, which have no scalar pair to carry it in) it
-// costs a round trip through a VGPR (v_cndmask 0,1 + v_cmp_ne) in every wave-step.
+// A lane without a record passes idx == kNoVoxel (its val is then not read).
+// ROUTE: the slab walks are built per route (kRouteAtomic / kRouteLog: walk_kernel's ROUTE, chosen by launch_walk from
+// P.log_idx), so a step holds one route's code and no test of which; the mesh walks test P.log_idx in every emit
+// (kRouteRuntime: they sit at their register limits and keep the code they had).
+constexpr int kRouteRuntime = 2;                  // beside Variant's kRouteAtomic / kRouteLog
 constexpr unsigned kLogExhausted = 0xfffffffeu;   // lg_chunk: this wave has found the log full (0xffffffff: no chunk claimed yet)
 constexpr unsigned kNoVoxel = 0xffffffffu;        // idx: no record
-template <int TALLY, bool IDX_MASK>
-LT_DEV void emit_deposit(const WalkParams& P, unsigned idx, typename TallyT<TALLY>::type val,
-                         unsigned& lg_cur, unsigned& lg_end, unsigned& lg_chunk, uint32_t* s_hist)
+
+// the wave's chunk is full (or it has none yet): close it and claim the next of the group's chunks, or find the log exhausted
+LT_DEV void log_claim(const WalkParams& P, unsigned& lg_cur, unsigned& lg_end, unsigned& lg_chunk)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned grp = blockIdx.x & (kLogGroups - 1);
+    if (lg_chunk < kLogExhausted && lane == 0) P.log_fill[lg_chunk] = lg_cur - lg_chunk * kLogChunk;
+    unsigned c = 0;
+    if (lane == 0) c = __hip_atomic_fetch_add(P.log_next + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    c = grp + kLogGroups * __builtin_amdgcn_readfirstlane(c);     // the group's own chunks: see kLogGroups
+    if (c < P.log_cap_chunks) { lg_chunk = c; lg_cur = c * kLogChunk; lg_end = lg_cur + kLogChunk; }
+    else { lg_chunk = kLogExhausted; lg_cur = lg_end = 0; }
+}
+
+// log exhausted: back to the linear voxel index and a global atomic
+template <int TALLY>
+LT_DEV void log_spill(const WalkParams& P, unsigned idx, typename TallyT<TALLY>::type val, bool has, unsigned cnt)
+{
+    if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(P.log_overflow, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (has) {
+        // (the divisors pass through an empty asm so that the reciprocal set-up of these divisions stays in this rare
+        // branch: left visible as loop invariants it was hoisted in front of the walk's loop and parked in registers)
+        unsigned ntx = P.log_ntx, nty = P.log_nty;
+        asm volatile("" : "+s"(ntx), "+s"(nty));
+        const unsigned tile = idx >> kTileShift, tx = tile % ntx, ty = (tile / ntx) % nty,
+                       tz = tile / (ntx * nty);
+        const unsigned vx = (tx << kTileBX) | (idx & 31u), vy = (ty << kTileBY) | ((idx >> 5) & 31u),
+                       vz = (tz << kTileBZ) | ((idx >> 10) & 15u);
+        tally_add<TALLY>(P.grid, (vz * (unsigned)P.ny + vy) * (unsigned)P.nx + vx, val);
+    }
+}
+
+// the wave's records (mask m, cnt of them), compacted by rank, to records [lg_cur, lg_cur + cnt) of its chunk
+template <int TALLY>
+LT_DEV void log_append(const WalkParams& P, unsigned idx, typename TallyT<TALLY>::type val, bool has, unsigned long long m,
+                       unsigned cnt, unsigned& lg_cur, uint32_t* s_hist)
 {
     typedef typename TallyT<TALLY>::type TV;
-    const bool has = idx != kNoVoxel;
-    unsigned long long m = 0;
-    if constexpr (IDX_MASK) m = __ballot(has);
-    if (P.log_idx == nullptr) {
-        if (has) tally_add<TALLY>(P.grid, idx, val);
-        return;
-    }
-    if constexpr (!IDX_MASK) m = __ballot(has);
-    if (m == 0ull) return;
-    const unsigned cnt = (unsigned)__popcll(m);
-    // (a wave that has found the log exhausted does not ask again: lg_chunk == kLogExhausted is sticky, so an undersized log
-    // costs each wave ONE extra returning atomic, not one per emit on 16 shared addresses, and the group counters stay
-    // within cap + resident waves -- far from wrapping grp + kLogGroups * c)
-    if (lg_chunk != kLogExhausted && lg_end - lg_cur < cnt) {
-        const int lane = threadIdx.x & 63;
-        const unsigned grp = blockIdx.x & (kLogGroups - 1);
-        if (lg_chunk < kLogExhausted && lane == 0) P.log_fill[lg_chunk] = lg_cur - lg_chunk * kLogChunk;
-        unsigned c = 0;
-        if (lane == 0) c = __hip_atomic_fetch_add(P.log_next + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        c = grp + kLogGroups * __builtin_amdgcn_readfirstlane(c);     // the group's own chunks: see kLogGroups
-        if (c < P.log_cap_chunks) { lg_chunk = c; lg_cur = c * kLogChunk; lg_end = lg_cur + kLogChunk; }
-        else { lg_chunk = kLogExhausted; lg_cur = lg_end = 0; }
-    }
-    if (lg_chunk == kLogExhausted) {  // log exhausted: back to the linear voxel index and a global atomic
-        if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(P.log_overflow, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (has) {
-            // (the divisors pass through an empty asm so that the reciprocal set-up of these divisions stays in this rare
-            // branch: left visible as loop invariants it was hoisted in front of the walk's loop and parked in registers)
-            unsigned ntx = P.log_ntx, nty = P.log_nty;
-            asm volatile("" : "+s"(ntx), "+s"(nty));
-            const unsigned tile = idx >> kTileShift, tx = tile % ntx, ty = (tile / ntx) % nty,
-                           tz = tile / (ntx * nty);
-            const unsigned vx = (tx << kTileBX) | (idx & 31u), vy = (ty << kTileBY) | ((idx >> 5) & 31u),
-                           vz = (tz << kTileBZ) | ((idx >> 10) & 15u);
-            tally_add<TALLY>(P.grid, (vz * (unsigned)P.ny + vy) * (unsigned)P.nx + vx, val);
-        }
-        return;
-    }
     if (has) {
         const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
         P.log_idx[lg_cur + rank] = idx;
@@ -180,6 +176,45 @@ LT_DEV void emit_deposit(const WalkParams& P, unsigned idx, typename TallyT<TALL
         atomicAdd(&s_hist[idx >> P.log_hist_shift], 1u);   // histogram of the first partition pass's bins, kept in LDS
     }
     lg_cur += cnt;
+}
+
+template <int TALLY, int ROUTE>
+LT_DEV void emit_deposit(const WalkParams& P, unsigned idx, typename TallyT<TALLY>::type val,
+                         unsigned& lg_cur, unsigned& lg_end, unsigned& lg_chunk, uint32_t* s_hist)
+{
+    const bool has = idx != kNoVoxel;
+    if constexpr (ROUTE == kRouteAtomic) {
+        if (has) tally_add<TALLY>(P.grid, idx, val);
+    } else if constexpr (ROUTE == kRouteLog) {
+        // The mask of records is the ballot of the integer compare: the v_cmp itself, into a scalar pair.  With room in the chunk
+        // an append passes ONE wave-uniform test, of the room.  A wave that has found the log exhausted keeps an empty chunk
+        // (lg_cur == lg_end == 0), so the same test sends every later emit of it into the rare block, where the state is looked at:
+        // lg_chunk == kLogExhausted is sticky, so an undersized log costs each wave ONE extra returning atomic, not one per emit on
+        // 16 shared addresses, and the group counters stay within cap + resident waves -- far from wrapping grp + kLogGroups * c.
+        // The rare block is an excursion that comes back in front of the append (a wave that spilled appends nothing: no lane,
+        // no record), so the append's path holds no join with it and no flag that says which way the wave came.
+        bool rec = has;
+        const unsigned long long m = __ballot(has);
+        if (m == 0ull) return;
+        unsigned cnt = (unsigned)__popcll(m);
+        if (__builtin_expect(lg_end - lg_cur < cnt, 0)) {      // once per kLogChunk records -- or the log is exhausted
+            if (lg_chunk != kLogExhausted) log_claim(P, lg_cur, lg_end, lg_chunk);
+            if (lg_chunk == kLogExhausted) { log_spill<TALLY>(P, idx, val, has, cnt); rec = false; cnt = 0; }
+        }
+        log_append<TALLY>(P, idx, val, rec, m, cnt, lg_cur, s_hist);
+    } else {
+        if (P.log_idx == nullptr) {
+            if (has) tally_add<TALLY>(P.grid, idx, val);
+            return;
+        }
+        // (the mask from the bool behind the branch: these kernels have no scalar pair to carry it across in)
+        const unsigned long long m = __ballot(has);
+        if (m == 0ull) return;
+        const unsigned cnt = (unsigned)__popcll(m);
+        if (lg_chunk != kLogExhausted && lg_end - lg_cur < cnt) log_claim(P, lg_cur, lg_end, lg_chunk);
+        if (lg_chunk == kLogExhausted) { log_spill<TALLY>(P, idx, val, has, cnt); return; }
+        log_append<TALLY>(P, idx, val, has, m, cnt, lg_cur, s_hist);
+    }
 }
 
 constexpr unsigned kPacket = 64;  // photon ids taken from the global queue per atomic
@@ -280,23 +315,38 @@ typedef void (*WalkFn)(const WalkParams);
 // CAPTURE (light sub-path vertices, f4) is a compile-time variant: the capture code costs the plain walk registers
 // even behind a never-taken branch (36-84 B of scratch per lane, walk 29.7 -> 34.6 ms when it was a run-time test).
 // Captures run the f64 walk with the XORWOW generator.
+// slabs: walk_kernel, a build per deposit route (Variant::route) -- of what lt_launch can ask for: the log carries neither
+// table-RNG walks nor captures nor the diagnostic build without a tally; the bulk kernel (PHASE 1) fills a log, the tail kernel
+// (PHASE 2) deposits with atomics.  Anything else is no kernel, and a launch of it an error.
+template <typename R, bool TABLE, bool CAPTURE, int PHASE, int ROUTE>
+static WalkFn pick_slab(int tally)
+{
+    constexpr bool kBuilt = (ROUTE == kRouteLog ? !TABLE && !CAPTURE && PHASE != 2 : PHASE != 1) && (PHASE == 0 || (!TABLE && !CAPTURE));
+    if constexpr (kBuilt) {
+        switch (tally) {
+        case LT_TALLY_F32:
+            if constexpr (TABLE) return nullptr;
+            else return walk_kernel<R, 0, TABLE, LT_TALLY_F32, CAPTURE, PHASE, ROUTE>;
+        case LT_TALLY_F64: return walk_kernel<R, 0, TABLE, LT_TALLY_F64, CAPTURE, PHASE, ROUTE>;
+        case LT_TALLY_U64FX: return walk_kernel<R, 0, TABLE, LT_TALLY_U64FX, CAPTURE, PHASE, ROUTE>;
+        case LT_TALLY_NONE:
+            if constexpr (!TABLE && !CAPTURE && PHASE == 0 && ROUTE == kRouteAtomic) return walk_kernel<R, 0, false, LT_TALLY_NONE, false, 0, kRouteAtomic>;
+            else return nullptr;
+        }
+    }
+    return nullptr;
+}
+
+// meshes: walk_kernel_q (the same body with batched BVH queries, lt_walk_kernel.inc)
 template <typename R, int GEOM, bool TABLE, bool CAPTURE>
 static WalkFn pick_tally(int tally)
 {
     switch (tally) {
-    // slabs: walk_kernel; meshes: walk_kernel_q (the same body with batched BVH queries, lt_walk_kernel.inc)
     case LT_TALLY_F32:
         if constexpr (TABLE) return nullptr;
-        else if constexpr (GEOM == 0) return walk_kernel<R, GEOM, TABLE, LT_TALLY_F32, CAPTURE>;
         else return walk_kernel_q<R, GEOM, TABLE, LT_TALLY_F32, CAPTURE>;
-    case LT_TALLY_F64:
-        if constexpr (GEOM == 0) return walk_kernel<R, GEOM, TABLE, LT_TALLY_F64, CAPTURE>;
-        else return walk_kernel_q<R, GEOM, TABLE, LT_TALLY_F64, CAPTURE>;
-    case LT_TALLY_U64FX:
-        if constexpr (GEOM == 0) return walk_kernel<R, GEOM, TABLE, LT_TALLY_U64FX, CAPTURE>;
-        else return walk_kernel_q<R, GEOM, TABLE, LT_TALLY_U64FX, CAPTURE>;
-    case LT_TALLY_NONE:
-        if constexpr (!TABLE && GEOM == 0 && !CAPTURE) return walk_kernel<R, GEOM, TABLE, LT_TALLY_NONE, false>; else return nullptr;
+    case LT_TALLY_F64: return walk_kernel_q<R, GEOM, TABLE, LT_TALLY_F64, CAPTURE>;
+    case LT_TALLY_U64FX: return walk_kernel_q<R, GEOM, TABLE, LT_TALLY_U64FX, CAPTURE>;
     }
     return nullptr;
 }
@@ -317,24 +367,13 @@ template <typename R, bool TABLE, bool CAPTURE>
 static WalkFn pick_geom(const Variant& v)
 {
     if (v.mesh == 3) { if constexpr (!TABLE) return pick_march<R, CAPTURE>(v.tally); else return nullptr; }
-    if (v.mesh == 0) return pick_tally<R, 0, TABLE, CAPTURE>(v.tally);
+    if (v.mesh == 0)
+        return v.route == kRouteLog ? pick_slab<R, TABLE, CAPTURE, 0, kRouteLog>(v.tally) : pick_slab<R, TABLE, CAPTURE, 0, kRouteAtomic>(v.tally);
     if (v.mesh == 1) return pick_tally<R, 1, TABLE, CAPTURE>(v.tally);
     if constexpr (!TABLE) return pick_tally<R, 2, TABLE, CAPTURE>(v.tally); else return nullptr;
 }
 
-// slab walks in two kernels (Variant::phase 1 / 2, lt_walk_kernel.inc "Tail split"): XORWOW, no capture
-template <typename R, int PHASE>
-static WalkFn pick_phase(int tally)
-{
-    switch (tally) {
-    case LT_TALLY_F32: return walk_kernel<R, 0, false, LT_TALLY_F32, false, PHASE>;
-    case LT_TALLY_F64: return walk_kernel<R, 0, false, LT_TALLY_F64, false, PHASE>;
-    case LT_TALLY_U64FX: return walk_kernel<R, 0, false, LT_TALLY_U64FX, false, PHASE>;
-    }
-    return nullptr;
-}
-
-// ... and the walk through a mesh in LDS (Variant::mesh 1)
+// the walk through a mesh in LDS in two kernels (Variant::phase 1 / 2, lt_walk_kernel.inc "Tail split"): XORWOW, no capture
 template <typename R, int PHASE>
 static WalkFn pick_phase_q(int tally)
 {
@@ -348,14 +387,19 @@ static WalkFn pick_phase_q(int tally)
 
 static WalkFn pick(const Variant& v)
 {
+    if (v.route != kRouteAtomic && v.route != kRouteLog) return nullptr;
     if (v.phase) {
         if (v.mesh > 1 || v.table || v.capture) return nullptr;
         if (v.mesh == 1) {
             if (v.phase == 1) return v.f32 ? pick_phase_q<float, 1>(v.tally) : pick_phase_q<double, 1>(v.tally);
             return v.f32 ? pick_phase_q<float, 2>(v.tally) : pick_phase_q<double, 2>(v.tally);
         }
-        if (v.phase == 1) return v.f32 ? pick_phase<float, 1>(v.tally) : pick_phase<double, 1>(v.tally);
-        return v.f32 ? pick_phase<float, 2>(v.tally) : pick_phase<double, 2>(v.tally);
+        if (v.phase == 1) {
+            if (v.route != kRouteLog) return nullptr;
+            return v.f32 ? pick_slab<float, false, false, 1, kRouteLog>(v.tally) : pick_slab<double, false, false, 1, kRouteLog>(v.tally);
+        }
+        if (v.route != kRouteAtomic) return nullptr;
+        return v.f32 ? pick_slab<float, false, false, 2, kRouteAtomic>(v.tally) : pick_slab<double, false, false, 2, kRouteAtomic>(v.tally);
     }
     if (v.capture) return (v.f32 || v.table) ? nullptr : pick_geom<double, false, true>(v);
     if (v.f32) return v.table ? nullptr : pick_geom<float, false, false>(v);
@@ -382,8 +426,10 @@ int walk_max_blocks_per_cu(const Variant& v, int threads, size_t lds_bytes)
     return nb;
 }
 
-hipError_t launch_walk(const WalkParams& Pin, const Variant& v, const LaunchCfg& cfg, hipStream_t s)
+hipError_t launch_walk(const WalkParams& Pin, const Variant& vin, const LaunchCfg& cfg, hipStream_t s)
 {
+    Variant v = vin;
+    v.route = Pin.log_idx ? kRouteLog : kRouteAtomic;      // the one place a launch's route is decided: the kernel that runs is the build for these parameters
     WalkFn fn = pick(v);
     if (!fn) return hipErrorInvalidValue;
     WalkParams P = Pin;

@@ -40,7 +40,9 @@
 #define LT_STEP_HG(xi) hg_sample_walk(xi, Mp)
 #define LT_STEP_G (Mp->g)
 #endif
-#if LT_WALK_BATCH != 2
+#if LT_WALK_BATCH == 0
+template <typename R, int GEOM, bool TABLE, int TALLY, bool CAPTURE, int PHASE, int ROUTE>      // ROUTE: kRouteAtomic / kRouteLog (emit_deposit)
+#elif LT_WALK_BATCH == 1
 template <typename R, int GEOM, bool TABLE, int TALLY, bool CAPTURE, int PHASE = 0>
 #else
 template <typename R, int GEOM, bool TABLE, int TALLY, bool CAPTURE>
@@ -62,6 +64,18 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
 #if LT_WALK_BATCH == 2
     constexpr int PHASE = 0;
 #endif
+    // Where the deposit records go.  Slab walks: fixed per build -- the log build computes the tiled voxel index alone and appends,
+    // the atomic build has no tile index, no log cursor and no histogram.  The bulk kernel (PHASE 1) exists to fill a log, the
+    // tail kernel (PHASE 2) deposits with atomics beside that log's reduction.  Mesh walks: P.log_idx, asked where it matters.
+#if LT_WALK_BATCH == 0
+    constexpr int kRoute = ROUTE;
+#define LT_HAS_LOG (ROUTE == kRouteLog)
+    static_assert(ROUTE == kRouteAtomic || ROUTE == kRouteLog, "walk_kernel is built per deposit route");
+    static_assert((PHASE != 1 || ROUTE == kRouteLog) && (PHASE != 2 || ROUTE == kRouteAtomic), "bulk kernel: log; tail kernel: atomics");
+#else
+    constexpr int kRoute = kRouteRuntime;
+#define LT_HAS_LOG P.log_idx
+#endif
 #if LT_WALK_PRIO
     // The walk is bound by VALU issue; the log reductions that share its CUs (another job's partition and tile reduce) are not.
     // Raised wave priority lets the walk's waves issue first and the co-runners fill what is left.
@@ -71,9 +85,9 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
     // GEOM 2: the mesh is too large for LDS -> triangles and nodes are read from global memory (they are
     // read-only and shared by every wave, so they live in the XCD L2s / Infinity Cache after first touch)
     const LdsLayout<R> L(P.n_media, P.n_layers, GEOM == 1 ? P.n_tris : 0, GEOM == 1 ? P.n_nodes : 0,
-                         P.log_idx ? P.log_n_hist : 0u, LT_WALK_BATCH == 2 ? 4 * sizeof(MarchWave<R>) : 0);
+                         LT_HAS_LOG ? P.log_n_hist : 0u, LT_WALK_BATCH == 2 ? 4 * sizeof(MarchWave<R>) : 0);
     uint32_t* s_hist = reinterpret_cast<uint32_t*>(lds_raw + L.off_hist);   // log mode: records per partition bin (<= 4 KiB)
-    if (P.log_idx) for (unsigned t = threadIdx.x; t < P.log_n_hist; t += blockDim.x) s_hist[t] = 0;
+    if (LT_HAS_LOG) for (unsigned t = threadIdx.x; t < P.log_n_hist; t += blockDim.x) s_hist[t] = 0;
     double* s_cnt = reinterpret_cast<double*>(lds_raw + L.off_cnt);
     const MedD<R>* s_med = reinterpret_cast<const MedD<R>*>(lds_raw + L.off_media);
     const R* s_zb = reinterpret_cast<const R*>(lds_raw + L.off_zb);
@@ -358,7 +372,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                 const unsigned long long am = __ballot(alive);
                 const unsigned na = (unsigned)__popcll(am);
                 if (na != 0u && na <= P.dump_max) {
-                    emit_deposit<TALLY, kSlabForm>(P, pend_idx, pend_val, lg_cur, lg_end, lg_chunk, s_hist);
+                    emit_deposit<TALLY, kRoute>(P, pend_idx, pend_val, lg_cur, lg_end, lg_chunk, s_hist);
                     pend_idx = kNoVoxel;
                     const int leader = __ffsll((long long)am) - 1;
                     unsigned base = 0;
@@ -827,12 +841,18 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                     // 2^24 (a lane outside it gets a meaningless index, which is not used).  Slab walks: two v_mad_u32_u24 (mad_u24).
                     // Mesh walks: __umul24 compiles to two v_mad_u64_u32 here -- the compiler keeps only the low 18 bits of the
                     // product and with that forgets the factors' width; the probe prices the two forms alike.
-                    unsigned tile;
-                    if constexpr (kSlabForm) tile = mad_u24(mad_u24(vz >> kTileBZ, P.log_nty, vy >> kTileBY), P.log_ntx, vx >> kTileBX);
-                    else tile = __umul24(__umul24(vz >> kTileBZ, P.log_nty) + (vy >> kTileBY), P.log_ntx) + (vx >> kTileBX);
-                    const unsigned idx = P.log_idx   // log mode: tiled index (see kTileBX); atomic mode: linear index
-                        ? ((tile << kTileShift) | ((vz & 15u) << 10) | ((vy & 31u) << 5) | (vx & 31u))
-                        : (vz * (unsigned)P.ny + vy) * (unsigned)P.nx + vx;
+                    // The index: tiled on the log route (see kTileBX), linear on the atomic one; a slab build holds its route's alone
+                    // (the log's linear index exists only where an exhausted log spills, log_spill).
+                    unsigned idx;
+                    if constexpr (kRoute == kRouteAtomic) idx = (vz * (unsigned)P.ny + vy) * (unsigned)P.nx + vx;
+                    else {
+                        unsigned tile;
+                        if constexpr (kSlabForm) tile = mad_u24(mad_u24(vz >> kTileBZ, P.log_nty, vy >> kTileBY), P.log_ntx, vx >> kTileBX);
+                        else tile = __umul24(__umul24(vz >> kTileBZ, P.log_nty) + (vy >> kTileBY), P.log_ntx) + (vx >> kTileBX);
+                        idx = kRoute == kRouteLog || P.log_idx
+                            ? ((tile << kTileShift) | ((vz & 15u) << 10) | ((vy & 31u) << 5) | (vx & 31u))
+                            : (vz * (unsigned)P.ny + vy) * (unsigned)P.nx + vx;
+                    }
                     const TV q = tally_quantum<TALLY, R>(w * LT_STEP_DEP);     // the tally quantity: absorbed weight, or w / mu_t (fluence)
                     const bool same = inside && idx == pend_idx;
                     const bool flush = inside && !same;
@@ -865,10 +885,10 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
         dg_clk_bnd += clock64() - dg_t1;
 #endif
         // wave-uniform point: send this step's records to the grid (atomics) or to the deposit log
-        emit_deposit<TALLY, kSlabForm>(P, f_idx, f_val, lg_cur, lg_end, lg_chunk, s_hist);
+        emit_deposit<TALLY, kRoute>(P, f_idx, f_val, lg_cur, lg_end, lg_chunk, s_hist);
     }
-    emit_deposit<TALLY, kSlabForm>(P, pend_idx, pend_val, lg_cur, lg_end, lg_chunk, s_hist);
-    if (P.log_idx && lg_chunk < kLogExhausted && (threadIdx.x & 63) == 0) P.log_fill[lg_chunk] = lg_cur - lg_chunk * kLogChunk;
+    emit_deposit<TALLY, kRoute>(P, pend_idx, pend_val, lg_cur, lg_end, lg_chunk, s_hist);
+    if (LT_HAS_LOG && lg_chunk < kLogExhausted && (threadIdx.x & 63) == 0) P.log_fill[lg_chunk] = lg_cur - lg_chunk * kLogChunk;
 
 #if LT_WALK_BATCH && defined(LT_DIAG_MESH)
 #if LT_WALK_BATCH == 2
@@ -908,7 +928,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
         __hip_atomic_fetch_add(&P.counters->steps, ws, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
-    if (P.log_idx)
+    if (LT_HAS_LOG)
         for (unsigned t = threadIdx.x; t < P.log_n_hist; t += blockDim.x)
             if (s_hist[t]) __hip_atomic_fetch_add(&P.log_hist[t * kLogGroups + (blockIdx.x & (kLogGroups - 1))], s_hist[t],
                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -918,6 +938,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
         __hip_atomic_fetch_add(&P.counters->w[threadIdx.x], s_cnt[threadIdx.x], __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
 }
+#undef LT_HAS_LOG
 #undef LT_STEP_ABSORB
 #if LT_WALK_BATCH == 0
 #undef LT_STEP_Y
