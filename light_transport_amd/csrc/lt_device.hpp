@@ -40,6 +40,15 @@ namespace ltk {
 // (80 SGPRs on top of the kernel's pointers and scalars), and the register allocator answered by spilling scalars into
 // VGPR lanes and restoring them with v_readlane -- VALU instructions -- every iteration (tens per photon-step once the
 // loop's other invariants had moved from VGPRs to kernel arguments).  Two scalar moves per use cost the VALU nothing.
+// a - b as an operation of its own: never contracted with the product that made b into one fused multiply-add.  The photon's
+// weight update w -= w * absorb is two rounded operations in the oracle; fused, w comes out one ulp away every few steps, and
+// one ulp of w moves a 2^-40 tally quantum whenever w * dep * 2^40 + 0.5 lands within it of an integer (about once in 10^7
+// deposits: tests/test_slab_as_mesh.py met one).  Same instruction count: the product is needed for the tally anyway.
+template <typename R> LT_DEV R sub_rounded(R a, R b)
+{
+#pragma clang fp contract(off)
+    return a - b;
+}
 #ifdef LT_K_IN_SGPR     /* A/B builds: the round-3 form, constants as "s" operands (loop invariants in scalar registers) */
 LT_DEV double fma_k(double a, double b, double k) { double r; asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(k)); return r; }
 LT_DEV double fma_mk(double a, double k, double c) { return __builtin_fma(a, k, c); }

@@ -861,7 +861,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                     pend_idx = flush ? idx : pend_idx;
                     acc_abs += inside ? (double)dw : 0.0;
                     acc_lost += inside ? 0.0 : (double)dw;
-                    w -= dw;
+                    w = sub_rounded(w, dw);
                     if (!(w > 0)) alive = false;
                     else {
                         R u[3] = {ux, uy, uz};
