@@ -306,6 +306,38 @@ int lt_tally_sum_columns(lt_ctx* ctx, const int32_t* bin_of_column, int n_bins, 
 int lt_radial_bins(int nx, int ny, const double origin_xy[2], const double voxel_xy[2], const double centre_xy[2], double dr,
                    int nr, int32_t* bins_out);
 
+/* ---- the tally convolved in x and y: the response to a beam of finite width ------ */
+/* The tally of a pencil beam on a laterally uniform medium (a layered slab) is the medium's response G(x, y, z); the response
+ * to a beam of profile S(x, y) is the convolution of G with S in x and y, plane by plane -- one traced run serves any number
+ * of beam sizes.  With W[z][y][x] the tally as weight (the units of lt_read_grid_f64: a u64 fixed-point element is
+ * (double)raw * 2^-40, an f32 element is widened) and W = 0 outside the grid,
+ *     out[z - z0][y][x] = sum over j, i of taps[j][i] * W[z][y - (j - kh/2)][x - (i - kw/2)]      for z0 <= z < z0 + nz_out
+ * -- a true convolution: the part of the beam displaced by (i - kw/2, j - kh/2) columns adds the pencil response displaced by the
+ * same amount.  LIMIT: weight that would have come from beyond the grid's edge is missing -- the grid has to hold G plus the
+ * beam, or the result is too small near the edges (never too large: the taps are non-negative).
+ * Every tap is finite and >= 0 (a beam profile has no other kind; the error bound of the sums rests on it), every tap count is
+ * odd and >= 1.  All three calls run on the ctx stream behind earlier launches, block until out is filled, and leave the grid,
+ * the counters and the statistics untouched.  Everything is computed in f64 with fused multiply-adds, without atomics, in an
+ * order that follows from the shapes alone: the same call on an unchanged grid returns identical bits, and a plane's bits do
+ * not depend on z0 / nz_out.  Device memory beyond the grid: the output planes asked for (and for the separable form one
+ * intermediate of the same size) in the ctx's scratch buffers -- nz_out is the means of staying small: one plane of a 512^3
+ * grid is 2 MiB.
+ * LT_E_STATE without a grid.  LT_E_INVALID: a tap that is negative, NaN or infinite; an even tap count or one below 1; a NULL
+ * pointer; z0 < 0, nz_out < 1 or z0 + nz_out > nz; a column outside the grid; n_columns < 1.  LT_E_UNSUPPORTED: a tap count or
+ * column count above the limit (the message names the number). */
+
+/* taps [kh][kw], kh and kw odd, 1 .. 63; out [nz_out][ny][nx].  One workgroup per 32 x 32 output tile holds the tile and its
+ * halo in LDS; a tile whose input region holds nothing costs its read alone. */
+int lt_tally_convolve(lt_ctx* ctx, const double* taps, int kh, int kw, int z0, int nz_out, double* out);
+/* The same with taps[j][i] = taps_y[j] * taps_x[i], as two one-dimensional passes -- x first, into an intermediate, then y: kw + kh
+ * multiply-adds per voxel instead of kw * kh (the intermediate is rounded: the result is that of the two passes, not bit for bit
+ * that of the outer product).  kh and kw odd, 1 .. 255. */
+int lt_tally_convolve_sep(lt_ctx* ctx, const double* taps_x, int kw, const double* taps_y, int kh, int z0, int nz_out, double* out);
+/* The convolved value at listed columns only, for every z: columns [n_columns][2] = (ix, iy) inside the grid, 1 <= n_columns <=
+ * 4096; out [nz][n_columns].  The depth profile on the beam's axis, or a lateral profile, in a few KiB and without a grid in
+ * between: the convolution's counterpart of lt_tally_sum_columns.  Taps as for lt_tally_convolve. */
+int lt_tally_convolve_at(lt_ctx* ctx, const double* taps, int kh, int kw, const int32_t* columns, int n_columns, double* out);
+
 /* ---- statistical error of the tally, from batch moments on the device --- */
 /* How far can a voxel's number be trusted?  Trace the photons in N batches of EQUAL size and close every batch with
  * lt_stats_fold.  With statistics on the ctx owns two more device buffers of the grid's extent: `prev`, the grid as it stood at

@@ -32,10 +32,15 @@ SYMBOLS = [
     "lt_last_log_info", "lt_set_tally_quantity", "lt_set_tuning", "lt_mesh_accel_info", "lt_build_bvh",
     "lt_layer_records", "lt_tally_sum_axes", "lt_tally_sum_columns", "lt_radial_bins", "lt_write_grid",
     "lt_stats_enable", "lt_stats_fold", "lt_stats_batches", "lt_stats_read_m2", "lt_stats_read_relerr", "lt_stats_summary",
+    "lt_tally_convolve", "lt_tally_convolve_sep", "lt_tally_convolve_at",
 ]
 _U64P = C.POINTER(C.c_uint64)
-# prototypes of the lt_stats_* entry points (lt.h); every one returns int
+_DP = C.POINTER(C.c_double)
+# prototypes of the lt_stats_* and lt_tally_convolve* entry points (lt.h); every one returns int
 PROTOTYPES = {
+    "lt_tally_convolve": [C.c_void_p, _DP, C.c_int, C.c_int, C.c_int, C.c_int, _DP],
+    "lt_tally_convolve_sep": [C.c_void_p, _DP, C.c_int, _DP, C.c_int, C.c_int, C.c_int, _DP],
+    "lt_tally_convolve_at": [C.c_void_p, _DP, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _DP],
     "lt_stats_enable": [C.c_void_p, C.c_int],
     "lt_stats_fold": [C.c_void_p],
     "lt_stats_batches": [C.c_void_p, _U64P],
@@ -233,6 +238,15 @@ def _ip(a):
 def _f64(a, shape=None):
     a = np.ascontiguousarray(a, dtype=np.float64)
     return a.reshape(shape) if shape is not None else a
+
+
+def _conv_taps(a, ndim, name):
+    """A tap array as the convolution calls take it: real numbers, ``ndim`` axes, not empty -> C-contiguous float64.  (What the
+    values and counts may be is the library's to check.)"""
+    t = np.asarray(a)
+    if t.dtype.kind not in "fiu" or t.ndim != ndim or t.size == 0:
+        raise LtError("%s: expected a non-empty %d-D array of real numbers, got %s %s" % (name, ndim, t.dtype.name, t.shape))
+    return np.ascontiguousarray(t, dtype=np.float64)
 
 
 class Context:
@@ -470,6 +484,41 @@ class Context:
         out, rawbuf, rp = self._sum_buffers((nz, max(int(n_bins), 0)), raw)
         self._ck(lib().lt_tally_sum_columns(self._h, _ip(b), C.c_int(int(n_bins)), _dp(out), rp), "lt_tally_sum_columns")
         return rawbuf if raw else out
+
+    # -- the tally convolved in x and y (lt.h: lt_tally_convolve*) --------------------------------------------------------
+    def tally_convolve(self, taps, z_range=None):
+        """float64 [nz_out, ny, nx]: the tally as weight, every plane convolved in x and y with ``taps`` -- a 2-D float64 array
+        [kh, kw] (odd counts up to 63), or a pair (taps_x, taps_y) of 1-D arrays (odd counts up to 255) for the separable
+        form, two 1-D passes.  Taps are finite and >= 0; weight from beyond the grid's edge is missing.  ``z_range`` = (z0,
+        nz_out): those planes only (default: all)."""
+        nz, ny, nx = self._grid_shape or (0, 0, 0)
+        z0, nz_out = (0, nz) if z_range is None else (int(z_range[0]), int(z_range[1]))
+        if self._grid_shape is not None and (z0 < 0 or nz_out < 1 or z0 + nz_out > nz):
+            raise LtError("tally_convolve: z_range = (z0, nz_out) = (%d, %d) does not lie inside 0 .. %d" % (z0, nz_out, nz))
+        out = np.empty((max(nz_out, 0), ny, nx), dtype=np.float64)
+        if isinstance(taps, (tuple, list)) and len(taps) == 2 and np.ndim(taps[0]) == 1 and np.ndim(taps[1]) == 1:
+            tx, ty = _conv_taps(taps[0], 1, "taps_x"), _conv_taps(taps[1], 1, "taps_y")
+            self._ck(lib().lt_tally_convolve_sep(self._h, _dp(tx), tx.size, _dp(ty), ty.size, z0, nz_out, _dp(out)), "lt_tally_convolve_sep")
+        else:
+            t = _conv_taps(taps, 2, "taps")
+            self._ck(lib().lt_tally_convolve(self._h, _dp(t), t.shape[0], t.shape[1], z0, nz_out, _dp(out)), "lt_tally_convolve")
+        return out
+
+    def tally_convolve_at(self, taps, columns):
+        """float64 [nz, n]: the convolved tally at the listed columns only, for every z.  ``taps``: 2-D [kh, kw], or a pair
+        (taps_x, taps_y), which is turned into its outer product; ``columns``: int [n, 2] of (ix, iy) inside the grid, n up to
+        4096."""
+        if isinstance(taps, (tuple, list)) and len(taps) == 2 and np.ndim(taps[0]) == 1 and np.ndim(taps[1]) == 1:
+            taps = np.outer(_conv_taps(taps[1], 1, "taps_y"), _conv_taps(taps[0], 1, "taps_x"))
+        t = _conv_taps(taps, 2, "taps")
+        cols = np.asarray(columns)
+        if cols.dtype.kind not in "iu" or cols.ndim != 2 or cols.shape[1] != 2 or cols.shape[0] < 1:
+            raise LtError("tally_convolve_at: columns must be an integer array [n, 2] of (ix, iy), n >= 1; got %s %s" % (cols.dtype.name, cols.shape))
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        nz = (self._grid_shape or (0, 0, 0))[0]
+        out = np.empty((nz, cols.shape[0]), dtype=np.float64)
+        self._ck(lib().lt_tally_convolve_at(self._h, _dp(t), t.shape[0], t.shape[1], _ip(cols), cols.shape[0], _dp(out)), "lt_tally_convolve_at")
+        return out
 
     # -- statistical error of the tally from batch moments (lt.h: lt_stats_*) ------------------------------------------
     def stats_enable(self, on=True):

@@ -1761,6 +1761,118 @@ int lt_tally_sum_columns(lt_ctx* c, const int32_t* bin_of_column, int n_bins, do
     return sum_read_back(c, n_out, out, raw_out);
 }
 
+// ---- the tally convolved in x and y on the device (kernels: lt_tallyconv.hip) ----
+namespace {
+// one axis of taps: an odd count of 1 .. most
+int conv_count_ok(lt_ctx* c, const char* who, const char* name, int n, int most)
+{
+    if (n < 1 || n % 2 == 0) return c->fail(LT_E_INVALID, "%s: %d taps along %s, need an odd count >= 1", who, n, name);
+    if (n > most) return c->fail(LT_E_UNSUPPORTED, "%s: %d taps along %s, at most %d", who, n, name, most);
+    return LT_OK;
+}
+// every tap finite and >= 0
+int conv_taps_ok(lt_ctx* c, const char* who, const char* name, const double* taps, size_t n)
+{
+    if (!taps) return c->fail(LT_E_INVALID, "%s: %s is required", who, name);
+    for (size_t i = 0; i < n; i++)
+        if (!(taps[i] >= 0.0) || std::isinf(taps[i]))
+            return c->fail(LT_E_INVALID, "%s: %s[%zu] is %g; taps are finite and >= 0", who, name, i, taps[i]);
+    return LT_OK;
+}
+int conv_range_ok(lt_ctx* c, const char* who, int z0, int nz_out)
+{
+    if (z0 < 0 || nz_out < 1 || (long long)z0 + nz_out > c->nz)
+        return c->fail(LT_E_INVALID, "%s: planes %d .. %lld, the grid has 0 .. %d", who, z0, (long long)z0 + nz_out - 1, c->nz - 1);
+    return LT_OK;
+}
+int conv_read_back(lt_ctx* c, size_t n_out, double* out)
+{
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch_out.p, n_out * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return LT_OK;
+}
+}  // namespace
+
+int lt_tally_convolve(lt_ctx* c, const double* taps, int kh, int kw, int z0, int nz_out, double* out)
+{
+    CHECK_CTX(c);
+    const char* who = "lt_tally_convolve";
+    if (!c->have_grid) return c->fail(LT_E_STATE, "%s: no grid", who);
+    if (!out) return c->fail(LT_E_INVALID, "%s: out is required", who);
+    int rc = conv_count_ok(c, who, "y", kh, kMaxConvTaps);
+    if (!rc) rc = conv_count_ok(c, who, "x", kw, kMaxConvTaps);
+    if (!rc) rc = conv_taps_ok(c, who, "taps", taps, (size_t)kh * (size_t)kw);
+    if (!rc) rc = conv_range_ok(c, who, z0, nz_out);
+    if (rc) return rc;
+    BIND(c);
+    const int kwp = conv_padded(kw);
+    std::vector<double> ft((size_t)kh * kwp, 0.0);      // flipped in both axes, rows zero-padded (lt_internal.hpp)
+    for (int j = 0; j < kh; j++)
+        for (int i = 0; i < kw; i++) ft[(size_t)j * kwp + i] = taps[(size_t)(kh - 1 - j) * kw + (kw - 1 - i)];
+    const size_t n_out = (size_t)nz_out * (size_t)c->ny * (size_t)c->nx;
+    HIP_TRY(c, c->d_scratch_out.ensure(n_out * 8));
+    rc = stage_in(c, c->d_scratch_aux, ft.data(), ft.size() * 8);
+    if (rc) return rc;
+    HIP_TRY(c, launch_tally_convolve(c->d_grid.p, c->tally, c->nx, c->ny, z0, nz_out, (const double*)c->d_scratch_aux.p, kh, kw,
+                                     (double*)c->d_scratch_out.p, c->stream));
+    return conv_read_back(c, n_out, out);      // waits for the stream: ft has been copied when it goes out of scope
+}
+
+int lt_tally_convolve_sep(lt_ctx* c, const double* taps_x, int kw, const double* taps_y, int kh, int z0, int nz_out, double* out)
+{
+    CHECK_CTX(c);
+    const char* who = "lt_tally_convolve_sep";
+    if (!c->have_grid) return c->fail(LT_E_STATE, "%s: no grid", who);
+    if (!out) return c->fail(LT_E_INVALID, "%s: out is required", who);
+    int rc = conv_count_ok(c, who, "x", kw, kMaxConvTapsSep);
+    if (!rc) rc = conv_count_ok(c, who, "y", kh, kMaxConvTapsSep);
+    if (!rc) rc = conv_taps_ok(c, who, "taps_x", taps_x, (size_t)kw);
+    if (!rc) rc = conv_taps_ok(c, who, "taps_y", taps_y, (size_t)kh);
+    if (!rc) rc = conv_range_ok(c, who, z0, nz_out);
+    if (rc) return rc;
+    BIND(c);
+    const int kwp = conv_padded(kw);
+    std::vector<double> ft((size_t)kwp + kh, 0.0);      // ftx [kwp], then fty [kh]
+    for (int i = 0; i < kw; i++) ft[i] = taps_x[kw - 1 - i];
+    for (int j = 0; j < kh; j++) ft[(size_t)kwp + j] = taps_y[kh - 1 - j];
+    const size_t n_out = (size_t)nz_out * (size_t)c->ny * (size_t)c->nx;
+    HIP_TRY(c, c->d_scratch_out.ensure(n_out * 8));
+    HIP_TRY(c, c->d_scratch_in.ensure(n_out * 8));
+    rc = stage_in(c, c->d_scratch_aux, ft.data(), ft.size() * 8);
+    if (rc) return rc;
+    const double* d_ft = (const double*)c->d_scratch_aux.p;
+    HIP_TRY(c, launch_tally_convolve_sep(c->d_grid.p, c->tally, c->nx, c->ny, z0, nz_out, d_ft, kw, d_ft + kwp, kh,
+                                         (double*)c->d_scratch_in.p, (double*)c->d_scratch_out.p, c->stream));
+    return conv_read_back(c, n_out, out);
+}
+
+int lt_tally_convolve_at(lt_ctx* c, const double* taps, int kh, int kw, const int32_t* columns, int n_columns, double* out)
+{
+    CHECK_CTX(c);
+    const char* who = "lt_tally_convolve_at";
+    if (!c->have_grid) return c->fail(LT_E_STATE, "%s: no grid", who);
+    if (!out) return c->fail(LT_E_INVALID, "%s: out is required", who);
+    int rc = conv_count_ok(c, who, "y", kh, kMaxConvTaps);
+    if (!rc) rc = conv_count_ok(c, who, "x", kw, kMaxConvTaps);
+    if (!rc) rc = conv_taps_ok(c, who, "taps", taps, (size_t)kh * (size_t)kw);
+    if (rc) return rc;
+    if (!columns || n_columns < 1) return c->fail(LT_E_INVALID, "%s: need a list of n_columns >= 1 columns", who);
+    if (n_columns > kMaxConvColumns) return c->fail(LT_E_UNSUPPORTED, "%s: %d columns, at most %d", who, n_columns, kMaxConvColumns);
+    for (int i = 0; i < n_columns; i++)
+        if (columns[2 * i] < 0 || columns[2 * i] >= c->nx || columns[2 * i + 1] < 0 || columns[2 * i + 1] >= c->ny)
+            return c->fail(LT_E_INVALID, "%s: column %d = (%d, %d) lies outside the %d x %d grid", who, i, columns[2 * i], columns[2 * i + 1],
+                           c->nx, c->ny);
+    BIND(c);
+    const size_t n_out = (size_t)c->nz * (size_t)n_columns;
+    HIP_TRY(c, c->d_scratch_out.ensure(n_out * 8));
+    rc = stage_in(c, c->d_scratch_aux, taps, (size_t)kh * kw * 8);
+    if (!rc) rc = stage_in(c, c->d_scratch_in, columns, (size_t)n_columns * 2 * sizeof(int32_t));
+    if (rc) return rc;
+    HIP_TRY(c, launch_tally_convolve_at(c->d_grid.p, c->tally, c->nx, c->ny, c->nz, (const double*)c->d_scratch_aux.p, kh, kw,
+                                        (const int32_t*)c->d_scratch_in.p, n_columns, (double*)c->d_scratch_out.p, c->stream));
+    return conv_read_back(c, n_out, out);
+}
+
 // ---- statistical error of the tally from batch moments (kernels: lt_tallystats.hip) ----
 #define STATS_ON(c, who) do { if (!(c)->stats_on) return (c)->fail(LT_E_STATE, "%s: statistics are off (lt_stats_enable)", who); } while (0)
 

@@ -1,6 +1,6 @@
 // lt_internal.hpp -- layouts and launcher declarations shared by the host API (lt_api.cpp, g++) and the gfx950 kernel
 // files (hipcc): lt_walk.hip, lt_query.hip, lt_render.hip (on the __device__ functions of lt_device.hpp) and lt_logtally.hip,
-// lt_tallysum.hip, lt_tallystats.hip (with lt_walk.hip on lt_tally.hpp); DESIGN.md section 1.  Not part of the public ABI.
+// lt_tallysum.hip, lt_tallystats.hip, lt_tallyconv.hip (with lt_walk.hip on lt_tally.hpp); DESIGN.md section 1.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -360,5 +360,22 @@ hipError_t launch_stats_relerr(const void* prev, const double* m2, int tally, si
 uint32_t stats_summary_parts(size_t n_vox, int tally);
 hipError_t launch_stats_summary(const void* prev, const double* m2, int tally, size_t n, uint64_t batches, const double* edges,
                                 int n_edges, void* partials, double* out, hipStream_t s);
+
+// The tally convolved in x and y (lt_tallyconv.hip).  All tap pointers are device copies, checked by the caller (finite, >= 0,
+// odd counts within the limits).  The tile kernel takes its taps FLIPPED in both axes, every row of kw taps zero-padded to
+// conv_padded(kw): ft [kh][conv_padded(kw)]; the separable form ftx [conv_padded(kw)] and fty [kh] (flipped, not padded), with
+// `mid` an intermediate of out's size.  grid: the whole tally; planes z0 .. z0 + nz_out - 1 are convolved into out
+// [nz_out][ny][nx].  The _at form takes taps [kh][kw] as the caller gave them and cols [n_cols][2] = (ix, iy) inside the grid;
+// out [nz][n_cols].
+constexpr int kMaxConvTaps = 63, kMaxConvTapsSep = 255, kMaxConvColumns = 4096;
+constexpr int kConvPad = 4;
+constexpr int conv_padded(int kw) { return (kw + kConvPad - 1) / kConvPad * kConvPad; }
+size_t tally_conv_lds_bytes(int kh, int kw);    // LDS of one workgroup of the tile kernel (kw = 0: the column pass of the separable form)
+hipError_t launch_tally_convolve(const void* grid, int tally, int nx, int ny, int z0, int nz_out, const double* ft, int kh, int kw,
+                                 double* out, hipStream_t s);
+hipError_t launch_tally_convolve_sep(const void* grid, int tally, int nx, int ny, int z0, int nz_out, const double* ftx, int kw,
+                                     const double* fty, int kh, double* mid, double* out, hipStream_t s);
+hipError_t launch_tally_convolve_at(const void* grid, int tally, int nx, int ny, int nz, const double* taps, int kh, int kw,
+                                    const int32_t* cols, int n_cols, double* out, hipStream_t s);
 
 }  // namespace ltk

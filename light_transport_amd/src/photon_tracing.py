@@ -14,6 +14,8 @@ array back, like ``render_scene(scene, primitives, bvh)``
 The walk itself (hop / drop / spin) runs in the HIP kernels
 behind include/lt.h; nothing here computes on the host.
 """
+import math
+
 import numpy as np
 
 from .. import _lib
@@ -104,6 +106,7 @@ class PhotonTracer:
     def __init__(self, device_id=0, ctx=None):
         self.ctx = ctx or _lib.Context(device_id)
         self.grid = None
+        self.geometry = self.source = None
         self.quantity = "absorbed"
         self.photons = 0          # traced since the last reset (the fluence normalisation)
         self._profiles = {}       # run_batches: keep mask -> [batches, sum of the per-batch sums, sum of their squares]
@@ -141,6 +144,7 @@ class PhotonTracer:
         ctx.set_vertex_capture(0)
         ctx.set_tally_quantity(quantity)     # "absorbed": weight absorbed per voxel; "fluence": w / mu_t per interaction
         self.grid, self.quantity, self.photons = grid, quantity, 0
+        self.geometry, self.source = geometry, source
         self._profiles = {}
         return self
 
@@ -266,6 +270,60 @@ class PhotonTracer:
         m = self.ctx.tally_sum_columns(bins, int(nr) + 1)
         edges = np.append(float(dr) * np.arange(int(nr) + 1), np.inf)
         return self._normalised(m, np.bincount(bins.ravel(), minlength=int(nr) + 1)[None, :]), edges
+
+    # -- the response to a beam of finite width: the tally convolved in x and y on the device ------------------------
+    def _beam_column(self, who):
+        """(ix, iy) of the column whose centre the pencil enters through -- or ValueError: the convolution of the tally with a
+        beam profile is the response to that beam only for a laterally invariant medium and taps centred on a column."""
+        if not isinstance(self.geometry, LayeredSlab):
+            raise ValueError("%s: needs a LayeredSlab (a laterally uniform medium), not %s" % (who, type(self.geometry).__name__))
+        src = self.source
+        if not isinstance(src, PencilBeam) or src.direction[0] != 0.0 or src.direction[1] != 0.0 or not src.direction[2] > 0.0:
+            raise ValueError("%s: needs a PencilBeam along +z (a beam normal to the layers)" % who)
+        col = []
+        for axis in (0, 1):
+            f = (src.position[axis] - self.grid.origin[axis]) / self.grid.voxel[axis]
+            k = math.floor(f)
+            if not abs(f - k - 0.5) <= 1e-6:
+                raise ValueError("%s: the pencil has to enter at the centre of a column of voxels (within 1e-6 of a voxel); along %s it "
+                                 "sits %.9g voxels from the column's edge" % (who, "xy"[axis], f - k))
+            col.append(int(k))
+        return tuple(col)
+
+    def beam_response(self, profile, z_range=None):
+        """float64 [nz_out, ny, nx]: the grid as a beam of ``profile`` (beam_profiles.GaussianProfile / FlatTopProfile, centred
+        where the pencil is) would have left it -- the traced pencil-beam tally convolved in x and y with the profile's taps on
+        the device (Context.tally_convolve), normalised exactly as absorbed() / fluence() normalise.  One run serves any number
+        of beam sizes.  ``z_range`` = (z0, nz_out): those planes only.
+        ValueError unless the geometry is a LayeredSlab, the source a PencilBeam along +z, and the pencil within 1e-6 of a
+        voxel of a column's centre: only then is the convolution the response to the beam.  A grid too narrow for the pencil
+        response plus the beam loses weight at its edges."""
+        self._beam_column("beam_response")
+        return self._beam_normalised(self.ctx.tally_convolve(profile.taps(self.grid.voxel[:2]), z_range))
+
+    def beam_profile_at(self, profile, columns=None):
+        """float64 [nz, n]: beam_response(profile) at the listed (ix, iy) columns only, for every z, without a grid in between
+        (Context.tally_convolve_at).  Default: the source's own column, so that [:, 0] is the depth profile on the axis of the
+        finite beam.  Refusals as for beam_response; at most 63 taps along an axis (Gaussian beams too: the taps go to the
+        device as their outer product)."""
+        col = self._beam_column("beam_profile_at")
+        if columns is None:
+            nx, ny, _ = self.grid.shape
+            if not (0 <= col[0] < nx and 0 <= col[1] < ny):
+                raise ValueError("beam_profile_at: the pencil's column %s lies outside the grid" % (col,))
+            columns = np.array([col], dtype=np.int32)
+        taps = profile.taps(self.grid.voxel[:2])
+        if isinstance(taps, tuple) and max(len(t) for t in taps) > 63:
+            raise ValueError("beam_profile_at: %d taps along an axis, lt_tally_convolve_at takes 63 (the separable form behind "
+                             "beam_response takes 255)" % max(len(t) for t in taps))
+        return self._beam_normalised(self.ctx.tally_convolve_at(taps, columns))
+
+    def _beam_normalised(self, weight):
+        if self.quantity != "fluence":
+            return weight
+        if self.photons <= 0:
+            raise ValueError("nothing traced since the last reset")
+        return weight / (self.grid.voxel_volume * float(self.photons))
 
     def absorbed_raw(self):
         return self.ctx.read_grid_raw()
