@@ -306,6 +306,28 @@ int lt_tally_sum_columns(lt_ctx* ctx, const int32_t* bin_of_column, int n_bins, 
 int lt_radial_bins(int nx, int ny, const double origin_xy[2], const double voxel_xy[2], const double centre_xy[2], double dr,
                    int nr, int32_t* bins_out);
 
+/* ---- parts of the tally: boxes, slices and coarser voxels ------------------ */
+/* A box of the grid, summed in blocks of bin[0] x bin[1] x bin[2] voxels: with bin = (1, 1, 1) a sub-volume or, one voxel
+ * thick, a slice (the plane through the beam); over the whole grid with bin > 1, the same volume at a coarser voxel size.  What
+ * lt_tally_sum_axes cannot give (it sums whole axes: the central plane is not a projection), without moving the grid to the host.
+ *   lo, size, bin   x, y, z order: the box's first voxel, its extent in voxels, the grid voxels per output voxel along each axis
+ *   out             C-order [oz][oy][ox] with o[a] = ceil(size[a] / bin[a])
+ * Output voxel (k, j, i) is the sum of the grid voxels with lo_z + k bz <= z < min(lo_z + (k + 1) bz, lo_z + size_z), likewise
+ * in y and x: the LAST BLOCK of an axis is clipped to the box, never padded (a bin beyond the box gives one block).
+ * Units and raw_out as for the sums above: out is f64 weight; raw_out (may be NULL; non-NULL only with LT_TALLY_U64FX, else
+ * LT_E_INVALID) the exact integer sums, out = (double)raw * 2^-40, wrapping modulo 2^64 -- ONE OUTPUT VOXEL holds at most 2^24
+ * units of weight.  Float tallies are widened to f64 and summed in f64.  No atomics; the order of every sum follows from (grid
+ * shape, lo, size, bin) alone: the same call on an unchanged grid returns identical bits, for float tallies too.  With bin = (1,
+ * 1, 1) an output voxel is the grid voxel converted exactly (an f64 tally: bit for bit), and the whole grid so read equals
+ * lt_read_grid_f64.
+ * Runs on the ctx stream behind earlier launches (as lt_read_grid is ordered), blocks until out is filled, and leaves the grid,
+ * the counters and the statistics untouched.  Device memory beyond the grid: the output (and the integer sums if asked for) in
+ * the ctx's scratch buffers; no partial sums.  Blocks below 512 voxels with bin_x <= 16 are summed by lanes that follow x (16
+ * bytes each, the rows of a block in registers, the bin_x neighbours through LDS); larger ones by one workgroup per output voxel.
+ * LT_E_STATE without a grid.  LT_E_INVALID: a NULL lo, size, bin or out; any lo < 0, size < 1 or bin < 1; a box that leaves the
+ * grid on any axis (lt_last_error names the axis and the value); raw_out with a float tally. */
+int lt_tally_box(lt_ctx* ctx, const int32_t lo[3], const int32_t size[3], const int32_t bin[3], double* out, uint64_t* raw_out);
+
 /* ---- the tally convolved in x and y: the response to a beam of finite width ------ */
 /* The tally of a pencil beam on a laterally uniform medium (a layered slab) is the medium's response G(x, y, z); the response
  * to a beam of profile S(x, y) is the convolution of G with S in x and y, plane by plane -- one traced run serves any number

@@ -32,12 +32,13 @@ SYMBOLS = [
     "lt_last_log_info", "lt_set_tally_quantity", "lt_set_tuning", "lt_mesh_accel_info", "lt_build_bvh",
     "lt_layer_records", "lt_tally_sum_axes", "lt_tally_sum_columns", "lt_radial_bins", "lt_write_grid",
     "lt_stats_enable", "lt_stats_fold", "lt_stats_batches", "lt_stats_read_m2", "lt_stats_read_relerr", "lt_stats_summary",
-    "lt_tally_convolve", "lt_tally_convolve_sep", "lt_tally_convolve_at",
+    "lt_tally_convolve", "lt_tally_convolve_sep", "lt_tally_convolve_at", "lt_tally_box",
 ]
 _U64P = C.POINTER(C.c_uint64)
 _DP = C.POINTER(C.c_double)
-# prototypes of the lt_stats_* and lt_tally_convolve* entry points (lt.h); every one returns int
+# prototypes of the lt_stats_*, lt_tally_convolve* and lt_tally_box entry points (lt.h); every one returns int
 PROTOTYPES = {
+    "lt_tally_box": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _DP, _U64P],
     "lt_tally_convolve": [C.c_void_p, _DP, C.c_int, C.c_int, C.c_int, C.c_int, _DP],
     "lt_tally_convolve_sep": [C.c_void_p, _DP, C.c_int, _DP, C.c_int, C.c_int, C.c_int, _DP],
     "lt_tally_convolve_at": [C.c_void_p, _DP, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _DP],
@@ -116,6 +117,26 @@ def keep_mask(keep):
 def kept_shape(mask, grid_shape):
     """Shape of tally_sum's result: the kept axes of grid_shape = (nz, ny, nx), in that order."""
     return tuple(n for n, bit in zip(grid_shape, (4, 2, 1)) if mask & bit)
+
+
+def _int_triple(v, name):
+    """``v`` as a tuple of three ints (x, y, z), or ValueError naming the argument."""
+    try:
+        t = tuple(v)
+    except TypeError:
+        t = ()
+    if len(t) != 3 or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) for k in t):
+        raise ValueError("%s=%r: three integers in x, y, z order" % (name, v))
+    return tuple(int(k) for k in t)
+
+
+def box_shape(size, bin=(1, 1, 1)):
+    """Shape (oz, oy, ox) of tally_box's result: ceil(size / bin) per axis, ``size`` and ``bin`` in x, y, z order (the last
+    block of an axis is clipped, a bin beyond the box gives one block)."""
+    s, b = _int_triple(size, "size"), _int_triple(bin, "bin")
+    if min(s) < 1 or min(b) < 1:
+        raise ValueError("box_shape: size=%r and bin=%r have to be >= 1 along every axis" % (size, bin))
+    return tuple(-(-s[a] // b[a]) for a in (2, 1, 0))
 
 
 def radial_bins(shape_xy, origin_xy, voxel_xy, centre_xy, dr, nr):
@@ -483,6 +504,21 @@ class Context:
             raise LtError("tally_sum_columns: bins must have shape (ny, nx) = %s, got %s" % ((ny, nx), b.shape))
         out, rawbuf, rp = self._sum_buffers((nz, max(int(n_bins), 0)), raw)
         self._ck(lib().lt_tally_sum_columns(self._h, _ip(b), C.c_int(int(n_bins)), _dp(out), rp), "lt_tally_sum_columns")
+        return rawbuf if raw else out
+
+    def tally_box(self, lo, size, bin=(1, 1, 1), raw=False):
+        """[oz, oy, ox] = box_shape(size, bin): the box of ``size`` voxels whose first voxel is ``lo`` (both x, y, z), every
+        ``bin`` = (bx, by, bz) grid voxels of it summed into one output voxel on the device; the last block of an axis is
+        clipped to the box.  bin (1, 1, 1): the sub-volume itself -- one voxel thick, a slice.  float64 weight; raw=True (u64
+        fixed-point tally only): the exact uint64 sums.  A box that leaves the grid: LtError."""
+        lo3, s3, b3 = _int_triple(lo, "lo"), _int_triple(size, "size"), _int_triple(bin, "bin")
+        big = [v for v in lo3 + s3 + b3 if not -2 ** 31 <= v < 2 ** 31]
+        if big:
+            raise ValueError("tally_box: %d does not fit an int32" % big[0])
+        shape = box_shape(s3, b3) if min(s3) >= 1 and min(b3) >= 1 else (0, 0, 0)       # (the library names what is wrong)
+        out, rawbuf, rp = self._sum_buffers(shape, raw)
+        arr = [(C.c_int32 * 3)(*v) for v in (lo3, s3, b3)]
+        self._ck(lib().lt_tally_box(self._h, arr[0], arr[1], arr[2], _dp(out), rp), "lt_tally_box")
         return rawbuf if raw else out
 
     # -- the tally convolved in x and y (lt.h: lt_tally_convolve*) --------------------------------------------------------

@@ -1761,6 +1761,33 @@ int lt_tally_sum_columns(lt_ctx* c, const int32_t* bin_of_column, int n_bins, do
     return sum_read_back(c, n_out, out, raw_out);
 }
 
+// ---- a part of the tally: a box, binned (kernels: lt_tallybox.hip) ---------
+int lt_tally_box(lt_ctx* c, const int32_t lo[3], const int32_t size[3], const int32_t bin[3], double* out, uint64_t* raw_out)
+{
+    CHECK_CTX(c);
+    const char* who = "lt_tally_box";
+    int rc = sum_outputs_ok(c, who, out, raw_out);
+    if (rc) return rc;
+    if (!lo || !size || !bin) return c->fail(LT_E_INVALID, "%s: lo, size and bin are required", who);
+    const int n[3] = {c->nx, c->ny, c->nz};
+    size_t n_out = 1;
+    for (int a = 0; a < 3; a++) {
+        if (lo[a] < 0) return c->fail(LT_E_INVALID, "%s: lo along %c is %d, below 0", who, "xyz"[a], lo[a]);
+        if (size[a] < 1) return c->fail(LT_E_INVALID, "%s: size along %c is %d, below 1", who, "xyz"[a], size[a]);
+        if (bin[a] < 1) return c->fail(LT_E_INVALID, "%s: bin along %c is %d, below 1", who, "xyz"[a], bin[a]);
+        if ((long long)lo[a] + size[a] > n[a])
+            return c->fail(LT_E_INVALID, "%s: the box covers %d .. %lld along %c, the grid has 0 .. %d", who, lo[a],
+                           (long long)lo[a] + size[a] - 1, "xyz"[a], n[a] - 1);
+        n_out *= ((size_t)size[a] + (size_t)bin[a] - 1) / (size_t)bin[a];
+    }
+    BIND(c);
+    HIP_TRY(c, c->d_scratch_out.ensure(n_out * (raw_out ? 16 : 8)));      // the integer sums only where they are asked for
+    double* d_out = (double*)c->d_scratch_out.p;
+    HIP_TRY(c, launch_tally_box(c->d_grid.p, c->tally, c->nx, c->ny, lo, size, bin, d_out,
+                                raw_out ? (unsigned long long*)(d_out + n_out) : nullptr, c->stream));
+    return sum_read_back(c, n_out, out, raw_out);
+}
+
 // ---- the tally convolved in x and y on the device (kernels: lt_tallyconv.hip) ----
 namespace {
 // one axis of taps: an odd count of 1 .. most

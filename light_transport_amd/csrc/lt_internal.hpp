@@ -378,4 +378,10 @@ hipError_t launch_tally_convolve_sep(const void* grid, int tally, int nx, int ny
 hipError_t launch_tally_convolve_at(const void* grid, int tally, int nx, int ny, int nz, const double* taps, int kh, int kw,
                                     const int32_t* cols, int n_cols, double* out, hipStream_t s);
 
+// A box of the tally, binned (lt_tallybox.hip).  lo, size, bin in x, y, z order, checked by the caller: lo >= 0, size and bin
+// >= 1, the box inside the nx x ny x nz grid.  out [oz][oy][ox] doubles with o = ceil(size / bin); raw (null unless the tally
+// is u64 fixed point) the integer sums.  No partial sums: nothing but out and raw is written.
+hipError_t launch_tally_box(const void* grid, int tally, int nx, int ny, const int32_t lo[3], const int32_t size[3], const int32_t bin[3],
+                            double* out, unsigned long long* raw, hipStream_t s);
+
 }  // namespace ltk

@@ -1,5 +1,6 @@
 // lt_tally.hpp -- the tally's three element types (f32 / f64 / u64 fixed point) in one place, for the walk (lt_walk.hip), the log
-// reduction (lt_logtally.hip), the whole-grid passes (lt_tallysum.hip) and the batch statistics (lt_tallystats.hip).
+// reduction (lt_logtally.hip), the whole-grid passes (lt_tallysum.hip), the batch statistics (lt_tallystats.hip) and the box
+// read-out (lt_tallybox.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -96,6 +96,20 @@ def uniform_table(n_photons, steps, seed=0):
     return np.random.RandomState(seed).rand(int(n_photons), int(steps), 4)
 
 
+def _box_key(lo, size, bin=(1, 1, 1)):
+    """(lo, size, bin) as three tuples of three ints in x, y, z order: what Context.tally_box takes, hashable."""
+    return tuple(_lib._int_triple(v, name) for v, name in ((lo, "lo"), (size, "size"), (bin, "bin")))
+
+
+def block_lengths(size, bin):
+    """int64 [ceil(size / bin)]: the voxels along one axis in every block of a box of ``size`` voxels binned by ``bin`` -- bin,
+    but for the last one, which is clipped to the box."""
+    if size < 1 or bin < 1:
+        raise ValueError("size = %d and bin = %d have to be >= 1" % (size, bin))
+    start = np.arange(0, size, bin, dtype=np.int64)
+    return np.minimum(start + bin, size) - start
+
+
 DEFAULT_MAX_STEPS = 1000000      # lt.h: the walk's hard cap (SURVEY Appendix C.8)
 
 
@@ -110,6 +124,7 @@ class PhotonTracer:
         self.quantity = "absorbed"
         self.photons = 0          # traced since the last reset (the fluence normalisation)
         self._profiles = {}       # run_batches: keep mask -> [batches, sum of the per-batch sums, sum of their squares]
+        self._regions = {}        # run_batches: (lo, size, bin) -> the same moments of a binned box
 
     def configure(self, geometry, grid, source, primitives=None, linear_bvh=None, max_steps=None, quantity="absorbed"):
         ctx = self.ctx
@@ -145,7 +160,7 @@ class PhotonTracer:
         ctx.set_tally_quantity(quantity)     # "absorbed": weight absorbed per voxel; "fluence": w / mu_t per interaction
         self.grid, self.quantity, self.photons = grid, quantity, 0
         self.geometry, self.source = geometry, source
-        self._profiles = {}
+        self._profiles, self._regions = {}, {}
         return self
 
     def run(self, n_photons, seed=0, photon_offset=0, rng_table=None, f32_walk=False, wait=True):
@@ -155,39 +170,43 @@ class PhotonTracer:
             self.ctx.sync()
         return self
 
-    def run_batches(self, n_photons, n_batches, seed=0, photon_offset=0, f32_walk=False, profiles=()):
+    def run_batches(self, n_photons, n_batches, seed=0, photon_offset=0, f32_walk=False, profiles=(), regions=()):
         """``n_photons`` traced as ``n_batches`` consecutive id ranges of equal size, every one closed with a fold of the batch
         statistics (turned on here if they are off): the grid ends as run(n_photons) leaves it, and relative_error() /
         error_summary() say how far every voxel can be trusted.  ``profiles``: keep-strings as tally_sum takes them ("z": the
         depth profile); for each, the device sum is taken after every fold and the moments of the per-batch differences are
         kept on the host for profile_error() -- voxels of one batch are correlated, so the error of a sum does not follow
-        from the per-voxel moments."""
+        from the per-voxel moments.  ``regions``: (lo, size, bin) triples as region() takes them; each box is read after every
+        fold in the same way, for region_error() -- the error of coarse voxels."""
         n_photons, n_batches = int(n_photons), int(n_batches)
         if n_batches < 2 or n_photons % n_batches:
             raise ValueError("run_batches: n_batches = %d must be at least 2 and divide n_photons = %d (equal batches)" % (n_batches, n_photons))
-        masks = [_lib.keep_mask(k) for k in profiles]
         ctx = self.ctx
+        raw = self.grid.dtype in ("u64fx", _lib.TALLY["u64fx"])
+        # what is summed after every fold: (the moments' dict, its key, the device sum)
+        sums = [(self._profiles, m, lambda m=m: ctx.tally_sum(m, raw=raw)) for m in (_lib.keep_mask(k) for k in profiles)]
+        sums += [(self._regions, r, lambda r=r: ctx.tally_box(*r, raw=raw)) for r in (_box_key(*r) for r in regions)]
         if not ctx.stats_enabled():
             ctx.stats_enable(True)
-            self._profiles = {}
-        raw = self.grid.dtype in ("u64fx", _lib.TALLY["u64fx"])
-        last = {}
-        for m in masks:      # where the profile stands before the first batch (zero, unless earlier batches were run)
-            last[m] = ctx.tally_sum(m, raw=raw)
-            if m not in self._profiles:
-                self._profiles[m] = [0, np.zeros(last[m].shape), np.zeros(last[m].shape)]
+            self._profiles.clear()
+            self._regions.clear()
+        last = []
+        for moments, key, read in sums:      # where a sum stands before the first batch (zero, unless earlier batches were run)
+            last.append(read())
+            if key not in moments:
+                moments[key] = [0, np.zeros(last[-1].shape), np.zeros(last[-1].shape)]
         per = n_photons // n_batches
         for b in range(n_batches):
             ctx.launch(per, seed=seed, photon_offset=int(photon_offset) + b * per, f32_walk=f32_walk)
             ctx.stats_fold()
-            for m in masks:
-                now = ctx.tally_sum(m, raw=raw)
-                d = (now - last[m]).astype(np.float64) * 2.0 ** -40 if raw else now - last[m]
-                mom = self._profiles[m]
+            for i, (moments, key, read) in enumerate(sums):
+                now = read()
+                d = (now - last[i]).astype(np.float64) * 2.0 ** -40 if raw else now - last[i]
+                mom = moments[key]
                 mom[0] += 1
                 mom[1] = mom[1] + d
                 mom[2] = mom[2] + d * d
-                last[m] = now
+                last[i] = now
         self.photons += n_photons
         ctx.sync()
         return self
@@ -211,10 +230,19 @@ class PhotonTracer:
         n, s1, s2 = self._profiles[m]
         return _lib.relative_error(n, s1, s2)
 
+    def region_error(self, lo, size, bin=(1, 1, 1)):
+        """The relative standard error of region(lo, size, bin) over the batches (same shape), from the moments run_batches
+        kept for a ``regions`` entry: _lib.relative_error(batches, sum, sum of squares)."""
+        key = _box_key(lo, size, bin)
+        if key not in self._regions:
+            raise ValueError("region_error%r: run_batches(..., regions=(%r,)) first" % (key, key))
+        n, s1, s2 = self._regions[key]
+        return _lib.relative_error(n, s1, s2)
+
     def reset(self):
         self.ctx.zero_tally()
         self.photons = 0
-        self._profiles = {}
+        self._profiles, self._regions = {}, {}
 
     def absorbed(self):
         """float64 [nz, ny, nx]: absorbed photon weight per voxel (configure(..., quantity="absorbed"))."""
@@ -270,6 +298,38 @@ class PhotonTracer:
         m = self.ctx.tally_sum_columns(bins, int(nr) + 1)
         edges = np.append(float(dr) * np.arange(int(nr) + 1), np.inf)
         return self._normalised(m, np.bincount(bins.ravel(), minlength=int(nr) + 1)[None, :]), edges
+
+    # -- parts of the grid read on the device: boxes, slices, coarser voxels (Context.tally_box) --------------------------
+    def region(self, lo, size, bin=(1, 1, 1)):
+        """(array [oz, oy, ox], (z_edges, y_edges, x_edges)): the box of ``size`` voxels that starts at voxel ``lo`` (both x, y,
+        z), every ``bin`` = (bx, by, bz) voxels summed into one on the device; the last block of an axis is clipped to the
+        box.  Absorbed weight per output voxel, or the mean fluence over the voxels that went into it (the clipped count).
+        The edges, o + 1 per axis, are in scene units: origin + voxel x index, the last one the box's end."""
+        lo, size, bin = _box_key(lo, size, bin)
+        lengths = [block_lengths(size[a], bin[a]) for a in range(3)]
+        voxels = lengths[2][:, None, None] * lengths[1][None, :, None] * lengths[0][None, None, :]
+        edges = tuple(self.grid.origin[a] + self.grid.voxel[a] * (lo[a] + np.append(0, np.cumsum(lengths[a]))) for a in (2, 1, 0))
+        return self._normalised(self.ctx.tally_box(lo, size, bin), voxels), edges
+
+    def slice(self, axis, index, bin=1):
+        """The plane of voxels at ``index`` along ``axis`` ("x", "y", "z" or 0, 1, 2 = z, y, x, as projection names it): [nz,
+        nx] for "y", [nz, ny] for "x", [ny, nx] for "z" -- not a sum along the axis, the plane itself.  ``bin``: an int, or one
+        per axis of the plane in x, y, z order, to bin it within the plane (region)."""
+        name = axis if isinstance(axis, str) else {0: "z", 1: "y", 2: "x", -1: "x", -2: "y", -3: "z"}.get(axis)
+        if name not in ("x", "y", "z"):
+            raise ValueError("slice(): axis must be 'x', 'y', 'z' or 0, 1, 2 (z, y, x), not %r" % (axis,))
+        a = "xyz".index(name)
+        inplane = list(bin) if np.ndim(bin) else [bin, bin]
+        if len(inplane) != 2:
+            raise ValueError("slice(): bin=%r: an int or one per axis of the plane" % (bin,))
+        lo, size, b3 = [0, 0, 0], list(self.grid.shape), inplane[:a] + [1] + inplane[a:]
+        lo[a], size[a] = index, 1
+        return np.squeeze(self.region(lo, size, b3)[0], axis=2 - a)
+
+    def coarse(self, bin):
+        """The whole grid at ``bin`` (an int, or (bx, by, bz)) times the voxel size: [ceil(nz / bz), ceil(ny / by), ceil(nx /
+        bx)], the last voxel of an axis smaller where bin does not divide it (region)."""
+        return self.region((0, 0, 0), self.grid.shape, bin if np.ndim(bin) else (bin,) * 3)[0]
 
     # -- the response to a beam of finite width: the tally convolved in x and y on the device ------------------------
     def _beam_column(self, who):
