@@ -157,7 +157,10 @@ int lt_set_source(lt_ctx* ctx, int type, const double pos[3], const double dir[3
 /* cap on a photon's steps: a photon alive after that many goes to w_capped with its weight (0: where it is emitted). */
 int lt_set_max_steps(lt_ctx* ctx, uint32_t max_steps);
 /* Experiment knobs -- tuning constants and diagnostic switches that tests and measurement tools vary; results do not
- * depend on any of them (the tests hold that down bit for bit).  value < 0 restores the built-in default.  Each knob is
+ * depend on any of them (the tests hold that down bit for bit, for the f64 and for the f32 walks: a shortcut in front of a
+ * surface query may only decline what the query itself would decline, so each compares with margins that cover the rounding
+ * of its own operands in walk precision -- the f32 plane pre-test with a slack that grows with |a - o| and with the
+ * triangle's conditioning, LT_FN_PLANE_REACH).  value < 0 restores the built-in default.  Each knob is
  * seeded ONCE, in lt_create, from the environment variable LT_<KEY IN CAPITALS>; the library reads the environment
  * nowhere else.  Keys:
  *   query_min          meshes in LDS: lanes a wave gathers before it serves their surface queries; meshes beyond LDS:
@@ -460,6 +463,7 @@ int lt_intersect_bounds(lt_ctx* ctx, const double* origins, const double* dirs,
 #define LT_FN_SPIN 7
 #define LT_FN_WALK_MATH 8 /* in: x in (0,1]  out: [5] -ln x, sin 2 pi x, cos 2 pi x, sqrt x, 1/(1+x) -- the walk's f64 primitives */
 #define LT_FN_WALK_MATH_RAW 9 /* in: k = a raw 32-bit draw (as a double)  out: [3] -ln u, sin 2 pi u, cos 2 pi u of u = (k + 1) 2^-32, by the forms the f64 XORWOW walk uses on the raw draw */
+#define LT_FN_PLANE_REACH 10 /* in: o[3], d[3], tri[3][3], s, f32 (0 / 1)  out: [2] reach, t -- the mesh walk's plane pre-test (1: a hop of length s from o along d may reach the triangle's plane; 0: rejected without a triangle test) and the triangle test's own t (NaN: none), both in walk precision (f32 != 0: float) on the triangle record a launch uploads.  o, d, s are narrowed to float as given: pass values a float holds.  The pre-test is sound when no row has reach = 0 with 1e-6 < t < s */
 int lt_eval(lt_ctx* ctx, int fn, const double* in, size_t n, double* out);
 /* first `count` raw 32-bit XORWOW outputs of photon `photon_id` under `seed`
  * (checks the per-photon seeding against the oracle's restatement) */

@@ -124,6 +124,7 @@ struct lt_ctx {
     int cn[3] = {0, 0, 0};
     double corg[3] = {0, 0, 0}, ccell[3] = {1, 1, 1};
     bool have_clear = false;
+    float reach_slack = 0.0f;      // largest reach_slack() of the mesh's f32 triangle records (upload_tables)
     // march grid (meshes whose f64 tables exceed the LDS budget): cell records, candidate lists, scratch of the builder
     DevBuf d_mcell, d_mlist, d_mcoarse, d_links;      // d_links: front-to-back threading of the BVH (bvh_octant_links)
     MarchGrid mgrid;
@@ -514,6 +515,8 @@ int upload_tables(lt_ctx* c)
         fill_nodes(c->nodes, n64); fill_nodes(c->nodes, n32);
         if ((rc = upload(c, c->d_tris[0], t64))) return rc;
         if ((rc = upload(c, c->d_tris[1], t32))) return rc;
+        c->reach_slack = 0.0f;      // the f32 plane pre-test's slack: the worst-conditioned triangle of the mesh
+        for (const TriD<float>& t : t32) c->reach_slack = std::max(c->reach_slack, reach_slack(t));
         if ((rc = upload(c, c->d_nodes[0], n64))) return rc;
         if ((rc = upload(c, c->d_nodes[1], n32))) return rc;
         c->have_links = bvh_octant_links(c->nodes, links16);
@@ -1328,6 +1331,7 @@ int lt_launch(lt_ctx* c, uint64_t n_photons, uint64_t photon_offset, uint64_t se
     P.counters = (DevCounters*)c->d_counters.p;
     if (c->knob.query_min >= 1 && c->knob.query_min <= 64) P.query_min = (unsigned)c->knob.query_min;
     if (c->have_mesh && c->have_clear) {
+        P.reach_slack = c->reach_slack;
         P.clear = (const uint4*)c->d_clear.p; P.cnx = c->cn[0]; P.cny = c->cn[1]; P.cnz = c->cn[2];
         for (int k = 0; k < 3; k++) {
             P.corg[k] = c->corg[k]; P.cinv[k] = 1.0 / c->ccell[k]; P.cdim[k] = (double)c->cn[k];
@@ -2100,11 +2104,31 @@ int lt_intersect_bounds(lt_ctx* c, const double* origins, const double* dirs, co
 int lt_eval(lt_ctx* c, int fn, const double* in, size_t n, double* out)
 {
     CHECK_CTX(c);
-    static const int k_in[10] = {2, 2, 3, 2, 8, 6, 8, 5, 1, 1}, k_out[10] = {1, 1, 6, 2, 4, 3, 5, 3, 5, 3};
-    if (fn < 0 || fn > 9) return c->fail(LT_E_INVALID, "lt_eval: unknown function %d", fn);
+    static const int k_in[11] = {2, 2, 3, 2, 8, 6, 8, 5, 1, 1, 21}, k_out[11] = {1, 1, 6, 2, 4, 3, 5, 3, 5, 3, 2};
+    if (fn < 0 || fn > 10) return c->fail(LT_E_INVALID, "lt_eval: unknown function %d", fn);
     if (n == 0) return LT_OK;
     if (!in || !out) return c->fail(LT_E_INVALID, "lt_eval: null argument");
     BIND(c);
+    std::vector<double> rows;
+    if (fn == LT_FN_PLANE_REACH) {      // rows of 17 in; the kernel takes the triangle as the TriD<R> a launch would upload
+        std::vector<double> v(9 * n);
+        const std::vector<int32_t> none(n, -1);
+        for (size_t i = 0; i < n; i++) std::memcpy(&v[9 * i], in + 17 * i + 6, 9 * sizeof(double));
+        std::vector<TriD<double>> t64; std::vector<TriD<float>> t32;
+        fill_tris(v, none, none, t64); fill_tris(v, none, none, t32);
+        rows.resize(21 * n);
+        for (size_t i = 0; i < n; i++) {
+            double* r = &rows[21 * i];
+            std::memcpy(r, in + 17 * i, 6 * sizeof(double));
+            const bool f32 = in[17 * i + 16] != 0.0;
+            for (int k = 0; k < 3; k++) {
+                r[6 + k] = f32 ? (double)t32[i].a[k] : t64[i].a[k]; r[9 + k] = f32 ? (double)t32[i].ab[k] : t64[i].ab[k];
+                r[12 + k] = f32 ? (double)t32[i].ac[k] : t64[i].ac[k]; r[15 + k] = f32 ? (double)t32[i].n[k] : t64[i].n[k];
+            }
+            r[18] = in[17 * i + 15]; r[19] = f32 ? 1.0 : 0.0; r[20] = f32 ? (double)reach_slack(t32[i]) : 0.0;
+        }
+        in = rows.data();
+    }
     int rc = stage_in(c, c->d_scratch_in, in, n * k_in[fn] * sizeof(double));
     if (rc) return rc;
     HIP_TRY(c, c->d_scratch_out.ensure(n * k_out[fn] * sizeof(double)));

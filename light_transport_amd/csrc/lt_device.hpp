@@ -604,17 +604,31 @@ LT_DEV void nearest_listed(const TriD<R>* tris, const NodeD<R>* nodes, int n_nod
 // way, so equal to this one up to rounding -- cannot lie inside (EPSILON, s): rays nearly parallel to the plane, where the
 // two parameters may differ by more than the margins, are always passed on.  On the Cornell cavity 89 % of the surface
 // queries find nothing -- a photon near a wall whose hop does not reach it -- and nearly all of those stop here.
-template <typename R> LT_DEV bool plane_within_reach(const TriD<R>* T, R px, R py, R pz, R ux, R uy, R uz, R s)
+// The margins are relative to t; the two parameters differ by an ABSOLUTE amount: both numerators, (a - o).n here and
+// ac.((o - a) x ab) there, are sums of products of size |a - o| that cancel down to the height over the plane, so they differ
+// by a few roundings of |a - o| |ab| |ac| / |ab x ac| (and n, rounded from the float64 normal, is not quite the normal of the
+// rounded edges: the same size), whatever the height.  In f64 that is 1e-15 of the scene, far below the 1e-7 of `behind` and of
+// the test's EPSILON.  In f32 it is 1e-6 of the scene: a hop that starts 1e-5 of the scene from a tilted facet was rejected
+// once in 10^3..10^4 hits.  The f32 test therefore widens both bounds by kslack (|ax - ox| + |ay - oy| + |az - oz|) and the
+// reach by s kslack (the same rounding in det), with kslack = 16 float roundings x |ab| |ac| / |ab x ac| from the host
+// (reach_slack below): then no hit of tri_hit is rejected at any scale.
+template <typename R> LT_DEV bool plane_within_reach(const TriD<R>* T, R px, R py, R pz, R ux, R uy, R uz, R s, R kslack)
 {
     const R nx = T->n[0], ny = T->n[1], nz = T->n[2];
     const R ddn = ux * nx + uy * ny + uz * nz;
-    const R dist = (T->a[0] - px) * nx + (T->a[1] - py) * ny + (T->a[2] - pz) * nz;      // = t * ddn
+    const R ax = T->a[0] - px, ay = T->a[1] - py, az = T->a[2] - pz;
+    const R dist = ax * nx + ay * ny + az * nz;      // = t * ddn
     const R addn = Mx<R>::abs(ddn);
     const R graze = sizeof(R) == 8 ? (R)1e-3 : (R)1e-2, behind = sizeof(R) == 8 ? (R)1e-7 : (R)1e-2,
             margin = sizeof(R) == 8 ? (R)(1.0 + 1e-4) : (R)(1.0 + 1e-2);
     if (!(addn > graze)) return true;
     const R tdd = ddn > 0 ? dist : -dist;       // t * |ddn|
-    return tdd >= -behind * addn && tdd <= s * addn * margin;
+    if constexpr (sizeof(R) == 8) {
+        return tdd >= -behind * addn && tdd <= s * addn * margin;
+    } else {
+        const R slack = kslack * (Mx<R>::abs(ax) + Mx<R>::abs(ay) + Mx<R>::abs(az));
+        return tdd >= -behind * addn - slack && tdd <= s * (addn * margin + kslack) + slack;
+    }
 }
 
 // The three decision uniforms a mesh walk holds while its step waits for a surface query: the f64 XORWOW walk keeps the raw

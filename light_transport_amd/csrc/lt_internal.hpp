@@ -65,6 +65,20 @@ struct TriD {
     int32_t med_front, med_back;
 };
 
+// kslack of the f32 plane pre-test (plane_within_reach, lt_device.hpp) for one triangle record: 16 roundings (8 float
+// epsilons) times the conditioning |ab| |ac| / |ab x ac| of the triangle test at vertex a.  A zero-area triangle is never hit
+// and asks for nothing.  A walk uses the largest value of its mesh (WalkParams::reach_slack).
+static inline float reach_slack(const TriD<float>& T)
+{
+    const double ab[3] = {T.ab[0], T.ab[1], T.ab[2]}, ac[3] = {T.ac[0], T.ac[1], T.ac[2]};
+    const double n[3] = {ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]};
+    const double n2 = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+    const double e2 = (ab[0] * ab[0] + ab[1] * ab[1] + ab[2] * ab[2]) * (ac[0] * ac[0] + ac[1] * ac[1] + ac[2] * ac[2]);
+    if (!(n2 > 0) || !(e2 > 0)) return 0.0f;
+    const double k = 8.0 * 1.1920928955078125e-07 * __builtin_sqrt(e2 / n2);
+    return k < 1e30 ? (float)k : 1e30f;
+}
+
 // Flattened BVH node: role of LinearBVHNode (bvh_new.py:60-67).
 template <typename R>
 struct NodeD {
@@ -202,6 +216,8 @@ struct WalkParams {
     lt_vertex* vertices;
     uint32_t* vertex_counts;
     unsigned max_vertices;
+    float reach_slack;    // f32 mesh walks in LDS: kslack of plane_within_reach, the largest reach_slack() of the mesh's triangles
+                          // (it sits in what was the struct's tail padding: no other member moves)
 };
 
 struct LaunchCfg {

@@ -67,6 +67,17 @@ __global__ void k_intersect_bounds(const double* o, const double* d, const doubl
     hit[i] = box_hit(lo, hi, oo, inv, tmax ? tmax[i] : __builtin_huge_val()) ? 1 : 0;
 }
 
+// one LT_FN_PLANE_REACH row: every value of it is representable in R (lt_eval narrowed the triangle; the caller rounds o, d, s)
+template <typename R> LT_DEV void plane_reach_pair(const double* r, double* out)
+{
+    const R o[3] = {(R)r[0], (R)r[1], (R)r[2]}, d[3] = {(R)r[3], (R)r[4], (R)r[5]};
+    TriD<R> T;
+    for (int k = 0; k < 3; k++) { T.a[k] = (R)r[6 + k]; T.ab[k] = (R)r[9 + k]; T.ac[k] = (R)r[12 + k]; T.n[k] = (R)r[15 + k]; }
+    T.med_front = T.med_back = -1;
+    out[0] = plane_within_reach<R>(&T, o[0], o[1], o[2], d[0], d[1], d[2], (R)r[18], (R)r[20]) ? 1.0 : 0.0;
+    out[1] = (double)tri_hit<R>(o, d, &T);
+}
+
 __global__ void k_eval(int fn, const double* in, size_t n, double* out)
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -114,6 +125,10 @@ __global__ void k_eval(int fn, const double* in, size_t n, double* out)
         const unsigned k = (unsigned)in[i];
         out[3 * i] = neg_log_raw(k, kWalkMathTab);
         sincos_turn_raw(k, kWalkMathTab, &out[3 * i + 1], &out[3 * i + 2]);
+    } break;
+    case LT_FN_PLANE_REACH: {   // the walk's plane pre-test beside the triangle test it stands in front of, in walk precision
+        const double* r = in + 21 * i;      // o[3], d[3], then the TriD fields a, ab, ac, n as the host filled them, s, f32, this triangle's reach_slack
+        if (r[19] != 0.0) plane_reach_pair<float>(r, out + 2 * i); else plane_reach_pair<double>(r, out + 2 * i);
     } break;
     }
 }

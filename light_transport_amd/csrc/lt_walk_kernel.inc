@@ -579,14 +579,17 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                     // length s < c ends before any surface and the traversal is skipped (same result, no query)
                     if (!(s < (R)clr)) {
                         // ... and a hop shorter than the cell's c2 can only hit the two triangles the record lists: if it cannot
-                        // even reach their planes (plane_within_reach: an exact rejection in front of tri_hit) there is no query
+                        // even reach their planes (plane_within_reach: a rejection in front of tri_hit that never rejects a hop
+                        // tri_hit would accept -- in f32 by the slack the host derived from the mesh) there is no query
                         bool need = true;
                         if constexpr (GEOM == 1) {
                             const float c2 = (float)__builtin_bit_cast(_Float16, (unsigned short)(rec_y & 0xffffu));
                             if (s < (R)c2) {
                                 const unsigned i0 = rec_z & 0xffffu, i1 = rec_z >> 16;
-                                need = (i0 != 0xffffu && plane_within_reach(&s_tris[i0], px, py, pz, ux, uy, uz, s)) ||
-                                       (i1 != 0xffffu && plane_within_reach(&s_tris[i1], px, py, pz, ux, uy, uz, s));
+                                R kslack = 0;
+                                if constexpr (sizeof(R) == 4) kslack = P.reach_slack;
+                                need = (i0 != 0xffffu && plane_within_reach(&s_tris[i0], px, py, pz, ux, uy, uz, s, kslack)) ||
+                                       (i1 != 0xffffu && plane_within_reach(&s_tris[i1], px, py, pz, ux, uy, uz, s, kslack));
                             }
                         }
                         if (need) { q_pend = true; q_u1 = h1; q_u2 = h2; q_u3 = h3; }

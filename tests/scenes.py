@@ -75,6 +75,39 @@ def cornell(n=64, **kw):
     return Problem(media, (n, n, n), (-dim, -dim, -dim), (voxel,) * 3, mesh=mesh, source=src, **kw)
 
 
+def transformed(prob, scale=1.0, shift=(0.0, 0.0, 0.0)):
+    """The same problem in other units and another frame: a new Problem in which every length x is x * scale + shift (grid
+    origin, z_bounds -- inf stays inf --, source position, mesh vertices, BVH bounds), every extent (voxel, the source's edge
+    vectors) is multiplied by scale and mu_a, mu_s are divided by it; g, n, directions, grid shape, max_steps and the medium
+    ids stay.  With scale a power of two and no shift every value is scaled exactly."""
+    scale = float(scale)
+    assert scale > 0
+    sh = np.asarray(shift, dtype=np.float64)
+
+    def move(x):
+        return np.asarray(x, dtype=np.float64) * scale + sh
+
+    media = [(m[0] / scale, m[1] / scale, m[2], m[3]) for m in prob.media]
+    layers = mesh = None
+    if prob.layers is not None:
+        layers = dict(prob.layers)
+        layers["z_bounds"] = [float(z) * scale + sh[2] for z in prob.layers["z_bounds"]]
+        layers["medium_idx"] = list(prob.layers["medium_idx"])
+    if prob.mesh is not None:
+        nodes = {k: np.array(v) for k, v in prob.mesh["nodes"].items()}
+        nodes["lo"], nodes["hi"] = move(nodes["lo"]), move(nodes["hi"])
+        mesh = dict(verts=move(prob.mesh["verts"]), med_front=prob.mesh["med_front"].copy(), med_back=prob.mesh["med_back"].copy(),
+                    nodes=nodes)
+        # every bound is a vertex coordinate: it went through the same rounding as the vertex
+        v = mesh["verts"].reshape(-1, 3)
+        assert np.array_equal(nodes["lo"][0], v.min(axis=0)) and np.array_equal(nodes["hi"][0], v.max(axis=0))
+    s = prob.source
+    src = dict(s, pos=tuple(float(x) for x in move(s["pos"])), dir=tuple(s["dir"]),
+               extra=tuple(float(x) * scale for x in s.get("extra", (0.0,) * 6)))
+    return Problem(media, tuple(prob.grid_shape), tuple(float(x) for x in move(prob.origin)),
+                   tuple(float(x) * scale for x in prob.voxel), layers=layers, mesh=mesh, source=src, max_steps=prob.max_steps)
+
+
 def assert_grid_close(g, go, rtol=1e-9, atol=1e-12, max_bad=0):
     d = np.abs(g - go)
     bad = int((d > atol + rtol * np.abs(go)).sum())
@@ -107,17 +140,20 @@ def icosphere(subdiv=3, radius=1.0, center=(0.0, 0.0, 0.0)):
     return np.array(v) * radius + np.asarray(center, dtype=np.float64), np.array(f, dtype=np.int64)
 
 
-def sphere_in_box(subdiv=4, n=48, split_method=0, **kw):
+def sphere_in_box(subdiv=4, n=48, split_method=0, balls=((1.5, (0.3, -0.2, 0.1)),), **kw):
     """f1 scene: a finely tessellated sphere (20 * 4^subdiv triangles; 5120 at subdiv 4 -- beyond the LDS
-    budget, so the walk traverses it in global memory) of an absorbing medium inside a closed box."""
+    budget, so the walk traverses it in global memory) of an absorbing medium inside a closed box.
+    balls: (radius, centre) of every sphere -- several disjoint ones give triangle counts between the powers of four."""
     from light_transport_amd.src.io import triangles_from_mesh
     dim = 4.0
     walls = cb.get_cornell_box(dim, K.GLASS_MAT, K.GLASS_MAT, K.GLASS_MAT) + cb.get_front_wall(dim, K.GLASS_MAT) \
         + cb.get_light_quad(dim, K.GLASS_MAT)
     for t in walls:
         t.med_front, t.med_back = 0, -1
-    vs, fs = icosphere(subdiv, 1.5, (0.3, -0.2, 0.1))
-    ball = triangles_from_mesh(vs, fs, K.GLASS_MAT)
+    ball = []
+    for radius, centre in balls:
+        vs, fs = icosphere(subdiv, radius, centre)
+        ball += triangles_from_mesh(vs, fs, K.GLASS_MAT)
     for t in ball:
         t.med_front, t.med_back = 0, 1
     ordered, linear = B.build_linear_bvh(walls + ball, split_method)
