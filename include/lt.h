@@ -172,12 +172,6 @@ int lt_set_max_steps(lt_ctx* ctx, uint32_t max_steps);
  *                      photons to the tail kernel when at most 32 lanes are alive) where a drain is exposed and the batch
  *                      has >= 512 photons per launched wave; n >= 2 = split with threshold n (<= 48) whatever the size
  *   part_alone         0 / 1: pin the partition build that shares the CU with a walk / the one for an otherwise idle device
- *   part_lds           one-pass grids (<= 1024 tiles): the partition that stages its NEXT item by LDS-DMA while it sorts this one
- *                      -- one workgroup per CU, 136 KiB of LDS, <= 62 VGPRs, no second workgroup needed to hide its loads
- *                      (on an idle device it equals the default build within 5 %).  Bits: 1 = use it where it applies; 2 = and
- *                      make lt_launch fail where it does not (two-pass grids; tests); 4 = the ONE-WAVE-PER-SIMD builds of the
- *                      partition (256 lanes, items of 2048 records, 68 KiB) and of the tile reduce (256 lanes) -- what fits
- *                      beside four walk waves of <= 112 VGPRs (measurement; DESIGN "Overlap")
  *   serial_walks       1: WALK TRAIN -- the walk kernels of every context of this device that sets the knob run one after
  *                      another (each waits for the end of the one enqueued before it; the log reductions stay on their own
  *                      streams).  For hosts that keep several jobs in flight: launch each walk at three of the four resident
@@ -186,11 +180,10 @@ int lt_set_max_steps(lt_ctx* ctx, uint32_t max_steps);
  *   render_lds_tables  0: lt_render_surface reads the scene tables from global memory even where they fit LDS (tests: the two
  *                      kernels give the same image bit for bit)
  *   -- taking effect when the mesh tables are next built (lt_set_mesh + launch / query):
- *   march_cells, march_scale_milli   march grid: cells along the longest axis / cell size in 1/1000 of the default
+ *   march_cells        march grid: cells along the longest axis
  *   clearance_cells    clearance grid of meshes in LDS: cells along the longest axis
  *   no_march, no_clearance, no_near_lists   switch the shortcut off (every query then takes the slower exact path)
- *   force_march        meshes that fit LDS take the march grid and walk_kernel_m all the same (measurement)
- *   march_info         print the march grid's dimensions when it is built */
+ *   force_march        meshes that fit LDS take the march grid and walk_kernel_m all the same (measurement) */
 int lt_set_tuning(lt_ctx* ctx, const char* key, int64_t value);
 /* LT_QUANTITY_*; applies to subsequent launches (the grid is NOT rescaled: zero it when switching) */
 int lt_set_tally_quantity(lt_ctx* ctx, int quantity);

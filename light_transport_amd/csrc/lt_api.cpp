@@ -147,21 +147,23 @@ struct lt_ctx {
     // them ONCE, in lt_create: nothing in this library reads the environment after that.
     struct Knobs {
         long query_min = -1, log_bits2 = -1, log_hot = -1, overlap_walk_bpc = -1, diag_no_tally = -1, log_timing = -1,
-             march_cells = -1, march_scale_milli = -1, no_march = -1, no_clearance = -1, no_near_lists = -1,
-             clearance_cells = -1, march_info = -1, force_march = -1, tail_split = -1, part_alone = -1, serial_walks = -1, part_lds = -1,
+             march_cells = -1, no_march = -1, no_clearance = -1, no_near_lists = -1,
+             clearance_cells = -1, force_march = -1, tail_split = -1, part_alone = -1, serial_walks = -1,
              render_lds_tables = -1;
         std::string overlap_pattern;      // LT_OVERLAP_PATTERN (relative sub-batch sizes; tools/pattern_ab.py)
     } knob;
+    // the keys of lt_set_tuning; lt_create walks the same table for the environment variables
+    struct KnobName { const char* key; long Knobs::*member; };
+    static constexpr KnobName kKnobNames[] = {
+        {"query_min", &Knobs::query_min}, {"log_bits2", &Knobs::log_bits2}, {"log_hot", &Knobs::log_hot},
+        {"overlap_walk_bpc", &Knobs::overlap_walk_bpc}, {"diag_no_tally", &Knobs::diag_no_tally}, {"log_timing", &Knobs::log_timing},
+        {"march_cells", &Knobs::march_cells}, {"no_march", &Knobs::no_march},
+        {"no_clearance", &Knobs::no_clearance}, {"no_near_lists", &Knobs::no_near_lists}, {"clearance_cells", &Knobs::clearance_cells},
+        {"force_march", &Knobs::force_march}, {"tail_split", &Knobs::tail_split}, {"part_alone", &Knobs::part_alone}, {"serial_walks", &Knobs::serial_walks},
+        {"render_lds_tables", &Knobs::render_lds_tables}};
     long* knob_by_name(const char* key)
     {
-        static const struct { const char* k; long Knobs::*m; } tab[] = {
-            {"query_min", &Knobs::query_min}, {"log_bits2", &Knobs::log_bits2}, {"log_hot", &Knobs::log_hot},
-            {"overlap_walk_bpc", &Knobs::overlap_walk_bpc}, {"diag_no_tally", &Knobs::diag_no_tally}, {"log_timing", &Knobs::log_timing},
-            {"march_cells", &Knobs::march_cells}, {"march_scale_milli", &Knobs::march_scale_milli}, {"no_march", &Knobs::no_march},
-            {"no_clearance", &Knobs::no_clearance}, {"no_near_lists", &Knobs::no_near_lists}, {"clearance_cells", &Knobs::clearance_cells},
-            {"march_info", &Knobs::march_info}, {"force_march", &Knobs::force_march}, {"tail_split", &Knobs::tail_split}, {"part_alone", &Knobs::part_alone}, {"serial_walks", &Knobs::serial_walks}, {"part_lds", &Knobs::part_lds},
-            {"render_lds_tables", &Knobs::render_lds_tables}};
-        for (const auto& t : tab) if (std::strcmp(key, t.k) == 0) return &(knob.*(t.m));
+        for (const KnobName& t : kKnobNames) if (std::strcmp(key, t.key) == 0) return &(knob.*(t.member));
         return nullptr;
     }
     bool on(long v) const { return v > 0; }
@@ -383,7 +385,7 @@ int build_march_grid(lt_ctx* c)
     if (!(longest > 0) || !std::isfinite(longest) || nt == 0) return LT_OK;
     // cell size ~ the median triangle's size (sqrt of twice its area): then a cell near the surface lists a handful of
     // triangles and a hop of a few triangle sizes crosses a handful of cells.  32 .. 256 cells along the longest axis;
-    // LT_MARCH_CELLS=<n> pins the number, LT_MARCH_SCALE=<x> scales the cell size (tuning).
+    // the knob march_cells pins the number (tuning).
     std::vector<double> size(nt);
     for (size_t i = 0; i < nt; i++) {
         const double* a = &c->verts[9 * i];
@@ -393,7 +395,6 @@ int build_march_grid(lt_ctx* c)
     }
     std::nth_element(size.begin(), size.begin() + nt / 2, size.end());
     double h = size[nt / 2];
-    if (c->knob.march_scale_milli > 10 && c->knob.march_scale_milli < 100000) h *= 1e-3 * (double)c->knob.march_scale_milli;
     int per_axis = h > 0 ? (int)std::lround(longest / h) : 256;
     per_axis = per_axis < 32 ? 32 : (per_axis > 256 ? 256 : per_axis);
     if (c->knob.march_cells >= 4 && c->knob.march_cells <= 512) per_axis = (int)c->knob.march_cells;
@@ -465,10 +466,6 @@ int build_march_grid(lt_ctx* c)
                                       (double*)c->d_mcoarse.p, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));      // rec / list are pageable host memory
     c->have_march = true;
-    if (c->on(c->knob.march_info))
-        std::fprintf(stderr, "[lt march] %zu triangles, grid %d x %d x %d (cell %.4g), %zu list entries (%.2f per triangle), %zu cells listed\n",
-                     nt, n[0], n[1], n[2], h, pairs.size(), (double)pairs.size() / (double)nt,
-                     (size_t)std::count_if(count.begin(), count.end(), [](uint32_t v) { return v != 0; }));
     return LT_OK;
 }
 
@@ -903,7 +900,6 @@ int run_log_plan(LogRun& R, const LogPlan& plan, uint64_t offset, int* n_batches
         // part_alone = 0 / 1 pins the build for A/B runs)
         L.alone = (plan.lanes == 1 && c->blocks_per_cu == 0 && !split) ? 1 : 0;
         if (c->knob.part_alone == 0 || c->knob.part_alone == 1) L.alone = (int)c->knob.part_alone;
-        L.lds_part = c->knob.part_lds > 0 ? (int)(c->knob.part_lds & 7) : 0;
         Variant vw = R.v;
         if (split) {
             const size_t cap = (size_t)cfg.blocks * (size_t)(cfg.threads / 64) * kDumpPoolLanes;      // every wave hands over at most that many
@@ -1033,13 +1029,10 @@ int lt_create(lt_ctx** out, int device_id)
     if (!c) { g_create_error = "out of host memory"; return LT_E_NOMEM; }
     c->device = device_id;
     {   // the one place the environment is read: LT_QUERY_MIN, LT_LOG_HOT, ... seed the knobs of lt_set_tuning
-        static const char* const names[] = {"query_min", "log_bits2", "log_hot", "overlap_walk_bpc", "diag_no_tally", "log_timing", "march_cells",
-                                            "march_scale_milli", "no_march", "no_clearance", "no_near_lists", "clearance_cells", "march_info", "force_march", "tail_split", "part_alone", "serial_walks", "part_lds",
-                                            "render_lds_tables"};
-        for (const char* k : names) {
+        for (const lt_ctx::KnobName& t : lt_ctx::kKnobNames) {
             std::string name = "LT_";
-            for (const char* q = k; *q; q++) name += (char)std::toupper((unsigned char)*q);
-            if (const char* v = std::getenv(name.c_str())) *c->knob_by_name(k) = std::atol(v);
+            for (const char* q = t.key; *q; q++) name += (char)std::toupper((unsigned char)*q);
+            if (const char* v = std::getenv(name.c_str())) c->knob.*(t.member) = std::atol(v);
         }
         if (const char* v = std::getenv("LT_OVERLAP_PATTERN")) c->knob.overlap_pattern = v;
     }

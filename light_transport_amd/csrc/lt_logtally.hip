@@ -385,239 +385,6 @@ __global__ void __launch_bounds__(kPartThreads, ALONE ? LT_PART_WAVES_ALONE : LT
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// The same counting sort for ONE workgroup per CU (one-pass grids; lt_set_tuning "part_lds").  k_log_part keeps an item in
-// registers and needs two workgroups per CU (2 x 8 waves, 2 x 128 VGPRs per SIMD lane) so that one's loads fly under the other's
-// LDS work -- at one workgroup per CU it is latency-bound (10 -> 25-34 ms), which is all the register quarter beside a walk
-// train offers it.  Here the NEXT item arrives by LDS-DMA (global_load_lds_dwordx4: no registers, the image is lane-linear,
-// i.e. a plain copy of the item) while this one is ranked, scanned and scattered: its 32 KiB of values into a second staging
-// buffer from the top of the item, its 16 KiB of indices into the ONE index buffer as soon as every wave holds this item's
-// indices in registers (after the ranking).  LDS: 16 + 2 x 32 KiB staging + 48 KiB sorted copy + 4 KiB of tables = 136 KiB,
-// which leaves three slab walk workgroups their 4.6 KiB each.  One vmcnt wait per item: where the cursor atomics' results are
-// needed -- the DMA was issued before them and vmcnt counts in order, so it has landed too; the item's own stores drain under
-// the next item's ranking.  Barriers are raw s_barrier with an lgkmcnt-only wait.  Measured (C2, 1.81e9 records): 10.5 ms
-// against k_log_part's 10.1-10.4 on an idle device (both ~3.8 TB/s: the bound is the scattered write-out, not latency -- 1024
-// lanes per workgroup changed nothing, and the per-phase clocks of tools/part_phases.py are flat).  THREADS = 256: one wave per
-// SIMD, items of 2048 records (8 per lane as at 512), 68 KiB -- the build that fits beside FOUR walk waves of <= 112 VGPRs
-// (14.3 ms alone).  No jobs-in-flight regime gains from either (DESIGN "Overlap": a walk loses about what the reduction beside
-// it takes, whatever registers it leaves) -- hence a knob, not the default.
-#ifdef LT_PART_PROF      // measurement builds only (tools/build_variant.sh): clock sums per phase of k_log_part_lds, first wave of every workgroup
-__device__ unsigned long long g_part_phase[8];
-#define LT_PP_DECL unsigned long long pp_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pp_t = __builtin_readcyclecounter()
-#define LT_PP(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); pp_[i] += t_ - pp_t; pp_t = t_; } while (0)
-#define LT_PP_FLUSH do { if (threadIdx.x == 0) for (int i_ = 0; i_ < 8; i_++) atomicAdd(&g_part_phase[i_], pp_[i_]); } while (0)
-#else
-#define LT_PP_DECL
-#define LT_PP(i)
-#define LT_PP_FLUSH
-#endif
-#define LT_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-constexpr uint32_t lds_part_item(int threads) { return threads >= 512 ? kPartItem : (uint32_t)threads * 8u; }
-template <typename TV, int THREADS>
-__global__ void __launch_bounds__(THREADS, 8) k_log_part_lds(LogReduceParams L)
-{
-#if LT_RED_PRIO      // (compile option: the log reduction's waves issue ahead of a walk's -- they need 8 % of its VALU work and sit on the critical path of their job)
-    __builtin_amdgcn_s_setprio(LT_RED_PRIO);
-#endif
-    constexpr uint32_t kItem = lds_part_item(THREADS), kItems = kLogChunk / kItem;      // records per item (8 per lane); items per log chunk
-    constexpr int kPerThread = (int)kItem / THREADS;      // (shadows the register-staged kernel's: 8 at 512 lanes, 4 at 1024)
-    constexpr uint32_t kPartThreads = THREADS;
-    constexpr int DPL = kMaxBins / THREADS > 2 ? kMaxBins / THREADS : 2;      // digits a lane owns in the scan
-    static_assert(kPerThread % 4 == 0 && DPL * THREADS >= kMaxBins, "a lane reads its records four at a time; the lanes own all digits");
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-    uint32_t* sK = reinterpret_cast<uint32_t*>(s_dyn);                                                           // [kItem] staged indices (ONE buffer: in registers after the ranking's first read)
-    TV* sV = reinterpret_cast<TV*>(s_dyn + (size_t)kItem * sizeof(uint32_t));                                 // [2][kItem] staged values
-    TV* oV = sV + 2 * (size_t)kItem;                                                                          // [kItem] digit-sorted values
-    uint32_t* oK = reinterpret_cast<uint32_t*>(oV + kItem);                                                   // [kItem] digit-sorted indices
-    uint32_t* s_a = oK + kItem;                                                                               // [kMaxBins + 2] counts -> offsets -> global bases
-    __shared__ uint32_t s_wsum[kPartThreads / 64];
-    const uint32_t nb = L.n_tiles;
-    const uint32_t n_units = claimed_chunks(L);
-    const uint32_t* in_idx = L.log_idx;
-    const TV* in_val = reinterpret_cast<const TV*>(L.log_val);
-    uint32_t* out_idx = L.tmp_idx;
-    TV* out_val = reinterpret_cast<TV*>(L.tmp_val);
-
-    // the items of this workgroup, in order: (first record, records) of every non-empty 4096-record half of its chunks.  Chunk
-    // fills come through the SCALAR cache (s_load: lgkmcnt): a vector load's result could only be awaited with vmcnt, and a
-    // vmcnt wait at the top of an item would also wait for the previous item's stores, which nothing else has to.
-    auto fill_of = [&](uint32_t u) -> uint32_t {
-        if (u >= n_units) return 0u;
-        uint32_t v;
-        const uint32_t* p_ = L.log_fill + u;
-        asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p_) : "memory");
-        return v;
-    };
-    uint32_t unit = blockIdx.x, sub = 0, fill = fill_of(unit);
-    auto settle = [&]() -> bool {      // move (unit, sub) to the next non-empty item at or after the current position
-        for (;;) {
-            if (unit >= n_units) return false;
-            if (sub < kItems && fill > sub * kItem) return true;
-            unit += gridDim.x; sub = 0; fill = fill_of(unit);
-        }
-    };
-    // One LDS-DMA wave-instruction: 64 lanes x 16 B from per-lane global addresses to LDS[dst + lane * 16] (M0 = dst, wave-uniform).
-    // Written as asm so that the compiler's wait-count pass does not know about it: through the builtin it drains the DMA
-    // (s_waitcnt vmcnt(0)) in front of the first LDS read that follows, i.e. at once.  The waits are placed by hand below;
-    // the compiler's own counted waits can only become stricter by operations it does not see.
-    auto glds16 = [](const void* gsrc, uint32_t lds_dst) {
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-    };
-    auto lds_addr = [](const void* p_) -> uint32_t {
-        return (uint32_t)__builtin_amdgcn_readfirstlane((int)(uintptr_t)(const __attribute__((address_space(3))) void*)p_);
-    };
-    auto stage_keys = [&](uint32_t lo) {               // LDS-DMA of the indices of the item that starts at record lo
-        const uint32_t tid_ = threadIdx.x, w = tid_ >> 6, l = tid_ & 63u;
-        constexpr uint32_t nk = kItem * sizeof(uint32_t) / (THREADS * 16);      // instructions per wave
-#pragma unroll
-        for (uint32_t j = 0; j < nk; j++)
-            glds16(in_idx + lo + (w * nk + j) * 256 + l * 4, lds_addr(sK + (w * nk + j) * 256));
-    };
-    auto stage_vals = [&](uint32_t lo, uint32_t buf) {      // ... and of its values, into staging buffer buf
-        const uint32_t tid_ = threadIdx.x, w = tid_ >> 6, l = tid_ & 63u;
-        constexpr uint32_t per = 16 / sizeof(TV), nj = kItem * sizeof(TV) / (THREADS * 16);      // values per lane per instruction; instructions per wave
-#pragma unroll
-        for (uint32_t j = 0; j < nj; j++)
-            glds16(in_val + lo + (w * nj + j) * (64 * per) + l * per, lds_addr(sV + buf * kItem + (w * nj + j) * (64 * per)));
-    };
-    if (!settle()) return;
-#if LT_PART_DROP == 9      // (measurement builds: no partition at all)
-    return;
-#endif
-    uint32_t buf = 0;
-    stage_keys(unit * kLogChunk + sub * kItem);
-    stage_vals(unit * kLogChunk + sub * kItem, buf);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    LT_PP_DECL;
-    for (;;) {
-        uint32_t tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));       // (lane-derived addresses and masks recomputed per item, not hoisted: see k_log_part)
-        const int lane = (int)(tid & 63u), wave = (int)(tid >> 6);
-        const uint32_t cur_unit = unit, n = fill - sub * kItem < kItem ? fill - sub * kItem : kItem;
-        sub++;
-        const bool have_next = settle();
-        uint32_t* cursor = L.cursor1 + (cur_unit & (kLogGroups - 1));
-        const uint32_t next_lo = unit * kLogChunk + sub * kItem;       // (meaningful if have_next)
-        const TV* vb = sV + buf * kItem;
-        // This item's DMA has landed: the first item's was awaited in front of the loop, every other one was issued BEFORE the
-        // previous item's cursor atomics, whose results were awaited there (vmcnt counts in order).  No vmcnt wait here: the
-        // previous item's stores drain under this item's ranking.
-        LT_LDS_BARRIER();                                     // every wave is done with the sorted copy and the other staging buffer
-        LT_PP(0);
-#if LT_PART_DROP != 3
-        if (have_next) stage_vals(next_lo, buf ^ 1u);
-#endif
-        for (uint32_t d = tid; d < nb + 2; d += kPartThreads) s_a[d] = 0;
-        LT_LDS_BARRIER();
-        LT_PP(1);
-        // ---- rank inside the digit
-        uint32_t key[kPerThread], ret2[kPerThread / 2];
-#pragma unroll
-        for (int g = 0; g < kPerThread / 4; g++) {
-            const uint4 q = *reinterpret_cast<const uint4*>(sK + (uint32_t)g * (kPartThreads * 4) + tid * 4);
-            key[4 * g] = q.x; key[4 * g + 1] = q.y; key[4 * g + 2] = q.z; key[4 * g + 3] = q.w;
-        }
-#pragma unroll
-        for (int r = 0; r < kPerThread; r++) {
-            const uint32_t k = (uint32_t)(r >> 2) * (kPartThreads * 4) + tid * 4 + (r & 3);
-#if LT_PART_DROP == 1      // (measurement builds: which of the partition's resources slows a walk beside it -- results are garbage)
-            const uint32_t rk = 0u;
-#else
-            const uint32_t rk = k < n ? atomicAdd(&s_a[tile_of(key[r])], 1u) : 0u;
-#endif
-            if (r & 1) ret2[r >> 1] |= rk << 16; else ret2[r >> 1] = rk;
-        }
-        LT_LDS_BARRIER();
-        LT_PP(2);
-#if LT_PART_DROP != 3
-        if (have_next) stage_keys(next_lo);      // every wave holds its indices in registers: the one index buffer takes the next item's
-#endif
-        // ---- space for every non-empty digit (one returning global atomic each), exclusive prefix over the digits
-        uint32_t c[DPL], g[DPL], incl, sum = 0;
-        {
-            const uint32_t d0 = DPL * tid;
-#pragma unroll
-            for (int i = 0; i < DPL; i++) { c[i] = d0 + i < nb ? s_a[d0 + i] : 0u; g[i] = 0; }
-#pragma unroll
-            for (int i = 0; i < DPL; i++) { if (c[i]) g[i] = atomicAdd(&cursor[(d0 + i) * kLogGroups], c[i]); sum += c[i]; }
-            incl = sum;
-#pragma unroll
-            for (int off2 = 1; off2 < 64; off2 <<= 1) { const uint32_t o = __shfl_up(incl, off2, 64); if (lane >= off2) incl += o; }
-            if (lane == 63) s_wsum[wave] = incl;
-        }
-        LT_LDS_BARRIER();
-        uint32_t ex = 0;
-        {
-            uint32_t before = 0;
-#pragma unroll
-            for (int w = 0; w < (int)(kPartThreads / 64); w++) before += w < wave ? s_wsum[w] : 0;
-            ex = before + incl - sum;
-            const uint32_t d0 = DPL * tid;
-            uint32_t run = ex;
-#pragma unroll
-            for (int i = 0; i < DPL; i++) { if (d0 + i < nb) s_a[d0 + i] = run; run += c[i]; }
-        }
-        LT_LDS_BARRIER();
-        LT_PP(3);
-        // ---- digit-sorted copy in LDS (values straight from the staging buffer)
-#pragma unroll
-        for (int g = 0; g < kPerThread / 4; g++) {
-            const Quad<TV> v = *reinterpret_cast<const Quad<TV>*>(vb + (uint32_t)g * (kPartThreads * 4) + tid * 4);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int r = 4 * g + j;
-                const uint32_t k = (uint32_t)g * (kPartThreads * 4) + tid * 4 + (uint32_t)j;
-                if (k < n) {
-                    const uint32_t p = s_a[tile_of(key[r])] + ((r & 1) ? ret2[r >> 1] >> 16 : (ret2[r >> 1] & 0xffffu));
-#if LT_PART_DROP == 4
-                    asm volatile("" :: "v"(p), "v"(v.v[j]));
-#else
-                    oK[p] = key[r]; oV[p] = v.v[j];
-#endif
-                }
-            }
-        }
-        LT_PP(4);
-        // (the bases are "used" on every path: were their only use under if (c0) / if (c1), the path "atomic issued, use skipped"
-        //  would exist for the compiler and it would wait for them -- vmcnt(0), the DMA with them -- before the next item's atomics)
-#pragma unroll
-        for (int i = 0; i < DPL; i++) asm volatile("" :: "v"(g[i]));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // ... and with them the next item's DMA, issued before them
-        LT_LDS_BARRIER();       // every lane has read its digits' offsets: the global bases take their place
-        {
-            const uint32_t d0 = DPL * tid;
-            uint32_t run = ex;
-#pragma unroll
-            for (int i = 0; i < DPL; i++) { if (c[i]) s_a[d0 + i] = g[i] - run; run += c[i]; }
-        }
-        LT_LDS_BARRIER();
-        LT_PP(5);
-        // ---- write out: consecutive sorted positions of one digit are consecutive in memory; the final pass keeps the
-        //      14-bit position inside the tile only (2 bytes)
-#pragma unroll
-        for (int i = 0; i < kPerThread; i++) {
-            const uint32_t p = tid + (uint32_t)i * kPartThreads;
-            if (p < n) {
-                const uint32_t kk = oK[p];
-                const uint32_t dst = s_a[tile_of(kk)] + p;
-#if LT_PART_DROP == 2
-                asm volatile("" :: "v"(dst), "v"(oV[p]));
-#else
-                reinterpret_cast<uint16_t*>(out_idx)[dst] = (uint16_t)(kk & (kTileSize - 1));
-                out_val[dst] = oV[p];
-#endif
-            }
-        }
-        LT_PP(6);
-        if (!have_next) break;
-        buf ^= 1u;
-        // (the barrier at the top of the next item separates these LDS reads from the next item's writes)
-    }
-    LT_PP_FLUSH;
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // Two-pass form: records per tile, counted from pass 1's output (indices only).  A workgroup takes up to kCountGroup
 // consecutive pass-2 items of ONE level-1 bin, counts their tiles in an LDS histogram of <= 128 entries and flushes it
 // with one global atomic per non-empty tile.
@@ -743,10 +510,9 @@ __device__ __forceinline__ void add8(AT* s_tile, const uint4 q, const Quad<TV>& 
     lds_add(&s_tile[q.w & m], (AT)b.v[2]); lds_add(&s_tile[(q.w >> 16) & m], (AT)b.v[3]);
 }
 
-template <typename TV, int THREADS>
-__global__ void __launch_bounds__(THREADS, LT_REDUCE_WAVES) k_log_reduce(LogReduceParams L)
+template <typename TV>
+__global__ void __launch_bounds__(kReduceThreads, LT_REDUCE_WAVES) k_log_reduce(LogReduceParams L)
 {
-    constexpr uint32_t kReduceThreads = THREADS;      // (512; 256 = one wave per SIMD, for the register quarter beside four 112-VGPR walk waves)
 #if LT_RED_PRIO      // (compile option: the log reduction's waves issue ahead of a walk's -- they need 8 % of its VALU work and sit on the critical path of their job)
     __builtin_amdgcn_s_setprio(LT_RED_PRIO);
 #endif
@@ -895,30 +661,9 @@ template <int PASS, bool HOT> static hipError_t launch_part(const LogReduceParam
 {
     return with_tally_type(L.tally, [&](auto t) { return launch_part_t<decltype(t), PASS, HOT>(L, s); });
 }
-template <typename TV, int THREADS> static hipError_t launch_part_lds_t(const LogReduceParams& L, hipStream_t s)
-{
-    const size_t lds = (size_t)lds_part_item(THREADS) * (3 * sizeof(TV) + 2 * sizeof(uint32_t)) + (size_t)(kMaxBins + 2) * sizeof(uint32_t);
-    const void* fn = reinterpret_cast<const void*>(&k_log_part_lds<TV, THREADS>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    static BlockCache blocks{};
-    unsigned grid = persistent_blocks(blocks, fn, THREADS, lds, 1) / kLogGroups * kLogGroups;      // one per CU; a workgroup serves one cursor group
-    if (grid < kLogGroups) grid = kLogGroups;
-    hipLaunchKernelGGL((k_log_part_lds<TV, THREADS>), dim3(grid), dim3(THREADS), lds, s, L);
-    return hipGetLastError();
-}
-template <int THREADS> static hipError_t launch_part_lds(const LogReduceParams& L, hipStream_t s)
-{
-    return with_tally_type(L.tally, [&](auto t) { return launch_part_lds_t<decltype(t), THREADS>(L, s); });
-}
 
 hipError_t launch_log_part1(const LogReduceParams& L, hipStream_t s)
 {
-    if (L.lds_part) {      // lt_set_tuning "part_lds": bit 0 = where it applies (one-pass grids), bit 1 = or fail (tests: proves the route), bit 2 = 1024 lanes
-        if (!L.dmap && L.bits2 == 0 && L.n_tiles <= (uint32_t)kMaxBins)
-            return (L.lds_part & 4) ? launch_part_lds<256>(L, s) : launch_part_lds<512>(L, s);
-        if (L.lds_part & 2) return hipErrorInvalidValue;
-    }
     if (L.dmap) {
         if (L.bits2 == 0 || L.n_tiles > kMaxHotTiles) return hipErrorInvalidValue;
         return launch_part<1, true>(L, s);
@@ -950,36 +695,21 @@ hipError_t launch_log_part2(const LogReduceParams& L, hipStream_t s)
     return launch_part<2, false>(L, s);
 }
 
-template <typename TV, int THREADS> static hipError_t launch_reduce_t(const LogReduceParams& L, hipStream_t s)
+template <typename TV> static hipError_t launch_reduce_t(const LogReduceParams& L, hipStream_t s)
 {
     const size_t lds = (size_t)kTileSize * sizeof(typename AccOf<TV>::type);
-    const void* fn = reinterpret_cast<const void*>(&k_log_reduce<TV, THREADS>);
+    const void* fn = reinterpret_cast<const void*>(&k_log_reduce<TV>);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     static BlockCache blocks{};
-    hipLaunchKernelGGL((k_log_reduce<TV, THREADS>), dim3(persistent_blocks(blocks, fn, THREADS, lds, 1)), dim3(THREADS), lds, s, L);
+    hipLaunchKernelGGL((k_log_reduce<TV>), dim3(persistent_blocks(blocks, fn, kReduceThreads, lds, 1)), dim3(kReduceThreads), lds, s, L);
     return hipGetLastError();
-}
-template <int THREADS> static hipError_t launch_reduce_n(const LogReduceParams& L, hipStream_t s)
-{
-    return with_tally_type(L.tally, [&](auto t) { return launch_reduce_t<decltype(t), THREADS>(L, s); });
 }
 hipError_t launch_log_reduce(const LogReduceParams& L, hipStream_t s)
 {
-    return (L.lds_part & 4) ? launch_reduce_n<256>(L, s) : launch_reduce_n<kReduceThreads>(L, s);
+    return with_tally_type(L.tally, [&](auto t) { return launch_reduce_t<decltype(t)>(L, s); });
 }
 
 }  // namespace ltk
-
-#ifdef LT_PART_PROF
-extern "C" int lt_diag_part_phases(unsigned long long* out8, int reset)
-{
-    if (hipDeviceSynchronize() != hipSuccess) return 1;
-    if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(ltk::g_part_phase), 8 * sizeof(unsigned long long)) != hipSuccess) return 2;
-    static const unsigned long long zero[8] = {};
-    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(ltk::g_part_phase), zero, sizeof(zero)) != hipSuccess) return 3;
-    return 0;
-}
-#endif

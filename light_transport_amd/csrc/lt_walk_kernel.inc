@@ -47,9 +47,6 @@ template <typename R, int GEOM, bool TABLE, int TALLY, bool CAPTURE, int PHASE =
 #else
 template <typename R, int GEOM, bool TABLE, int TALLY, bool CAPTURE>
 #endif
-#if LT_WALK_BATCH == 0 && defined(LT_SLAB_VGPR_CAP)
-__attribute__((amdgpu_num_vgpr(LT_SLAB_VGPR_CAP)))      // measurement builds: the slab walk within fewer registers (room for a reduction's wave beside four of the walk's)
-#endif
 __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLAB_WAVES : (GEOM == 2 ? LT_F64_GLOBAL_WAVES : LT_F64_WAVES)) : (GEOM == 0 ? LT_F32_WAVES : 4))) LT_WALK_NAME(const WalkParams P)
 {
     constexpr bool MESH = GEOM != 0;

@@ -4,10 +4,8 @@ run() { env $ENVS timeout -k 10 300 python bench.py --workload ${W:-c2} --inflig
 V=gpurun_ab/${VARIANT:-prio3}/liblt_hip.so
 LABEL="ship three_jobs" ENVS="A=1" run 3
 LABEL="prio three_jobs" ENVS="LT_HIP_LIBRARY=$V" run 3
-LABEL="prio three_jobs part_lds" ENVS="LT_HIP_LIBRARY=$V LT_PART_LDS=1" run 3
 LABEL="ship walk_train" ENVS="A=1" run 4
 LABEL="prio walk_train" ENVS="LT_HIP_LIBRARY=$V" run 4
-LABEL="prio walk_train part_lds" ENVS="LT_HIP_LIBRARY=$V LT_PART_LDS=1" run 4
 
 
 LABEL="ship one_call" ENVS="A=1" run 1
