@@ -404,6 +404,42 @@ int lt_stats_read_relerr(lt_ctx* ctx, double* out, size_t n_voxels);
 int lt_stats_summary(lt_ctx* ctx, const double* edges, int n_edges, uint64_t* voxels_out, double* weight_out,
                      uint64_t* raw_weight_out);
 
+/* ---- results by region: label volume, per-label totals, dose-volume histograms ------ */
+/* "How much did THIS structure absorb, where is its hottest voxel, what share of its volume got at least dose D?" -- without
+ * reading the grid back.  A label volume gives every voxel a region: labels [nz][ny][nx], one byte per voxel, each 0 ..
+ * n_labels - 1 or LT_LABEL_NONE for a voxel that is left out of everything; 1 <= n_labels <= 64.  lt_set_labels copies the volume
+ * into a device buffer the ctx owns (1 byte per voxel) and blocks until it has left the caller's array; labels == NULL releases
+ * it.  lt_set_grid drops the labels; lt_zero_tally, lt_write_grid and launches leave them alone.  WITHOUT labels both result
+ * calls treat the whole grid as label 0 with n_labels = 1: a plain histogram of the tally and a peak finder, with no setup.
+ * LT_E_STATE without a grid.  LT_E_INVALID: n_voxels that is not the grid's, n_labels outside 1 .. 64, a byte that is neither
+ * below n_labels nor LT_LABEL_NONE (checked on the host; lt_last_error names the first such flat index and its value). */
+#define LT_LABEL_NONE 255
+int lt_set_labels(lt_ctx* ctx, const uint8_t* labels, size_t n_voxels, int n_labels);
+/* n_labels_out: the n_labels in force, 0 when no labels are set */
+int lt_labels_info(lt_ctx* ctx, int* n_labels_out);
+/* Per label, [n_labels] each: weight_out the sum of its voxels in the units of lt_read_grid_f64; raw_out (may be NULL; non-NULL
+ * only with LT_TALLY_U64FX, else LT_E_INVALID) the exact integer sum, wrapping modulo 2^64, weight_out = (double)raw * 2^-40;
+ * voxels_out its voxels; filled_out those that are not zero; peak_out its largest voxel, converted exactly as lt_read_grid_f64
+ * converts a voxel; peak_index_out the LOWEST flat index (z * ny + y) * nx + x among its voxels that hold the peak -- an all-zero
+ * label reports its first voxel, a label without voxels index -1 and peak 0.  All but raw_out are required.  Counts, peaks,
+ * indices and the integer sums are exact; float weights as for lt_tally_histogram.  One pass over the grid and the labels; the
+ * workgroups that saw a label's peak read their part once more for its index (a tally is taken to be >= 0). */
+int lt_tally_label_sums(lt_ctx* ctx, double* weight_out, uint64_t* raw_out, uint64_t* voxels_out, uint64_t* filled_out,
+                        double* peak_out, int64_t* peak_index_out);
+/* The histogram of the tally per label.  edges as for lt_stats_summary: 1 <= n_edges <= 63 finite, non-negative, strictly
+ * ascending values (anything else LT_E_INVALID; more than 63 LT_E_UNSUPPORTED).  With v the voxel as weight (LT_TALLY_U64FX:
+ * (double)raw * 2^-40, one rounding; f32 widened) its class is the number of edges <= v.  voxels_out, weight_out (both required)
+ * and raw_weight_out [n_labels][n_edges + 1]: the voxels per (label, class) and the sum of their values.  The voxel counts, and
+ * with LT_TALLY_U64FX the weights, are integer sums: exact.  Float tallies are widened to f64 and added into per-workgroup bins
+ * with LDS atomics, then in a fixed order: the last bits may differ from call to call.  raw_weight_out: may be NULL; non-NULL only
+ * with LT_TALLY_U64FX (else LT_E_INVALID).  The cumulative dose-volume histogram V(>= edge k) is the reverse cumulative sum of a
+ * label's row on the host.
+ * Both result calls run on the ctx stream behind earlier launches (as lt_read_grid is ordered), block until the outputs are
+ * filled, leave the grid, the counters, the statistics and the labels untouched, and keep their partial sums in the ctx's
+ * scratch buffers.  LT_E_STATE without a grid, LT_E_INVALID on a NULL required pointer. */
+int lt_tally_histogram(lt_ctx* ctx, const double* edges, int n_edges, uint64_t* voxels_out, double* weight_out,
+                       uint64_t* raw_weight_out);
+
 int lt_grid_device_ptr(lt_ctx* ctx, void** ptr, size_t* bytes);
 int lt_counters_device_ptr(lt_ctx* ctx, void** ptr, size_t* bytes);
 void* lt_stream(lt_ctx* ctx); /* hipStream_t of the ctx */

@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("LT_HIP_LIBRARY") or os.path.join(_HERE, "liblt_hip.so
 TALLY = {"f32": 0, "f64": 1, "u64fx": 2}
 TALLY_NP = {0: np.float32, 1: np.float64, 2: np.uint64}
 FX_SCALE = 2.0 ** 40
+LABEL_NONE = 255      # LT_LABEL_NONE: a voxel of the label volume that is left out of everything
+MAX_LABELS = 64
 SRC_PENCIL, SRC_COSINE_QUAD = 0, 1
 FLAG_F32_WALK = 1
 FN = dict(HG_PDF=0, HG_SAMPLE=1, ONB=2, DISK=3, COSINE_HEMI=4, REFLECT=5, BOUNDARY=6, SPIN=7, WALK_MATH=8, WALK_MATH_RAW=9,
@@ -35,11 +37,16 @@ SYMBOLS = [
     "lt_layer_records", "lt_tally_sum_axes", "lt_tally_sum_columns", "lt_radial_bins", "lt_write_grid",
     "lt_stats_enable", "lt_stats_fold", "lt_stats_batches", "lt_stats_read_m2", "lt_stats_read_relerr", "lt_stats_summary",
     "lt_tally_convolve", "lt_tally_convolve_sep", "lt_tally_convolve_at", "lt_tally_box",
+    "lt_set_labels", "lt_labels_info", "lt_tally_label_sums", "lt_tally_histogram",
 ]
 _U64P = C.POINTER(C.c_uint64)
 _DP = C.POINTER(C.c_double)
-# prototypes of the lt_stats_*, lt_tally_convolve* and lt_tally_box entry points (lt.h); every one returns int
+# prototypes of the lt_stats_*, lt_tally_convolve*, lt_tally_box and label entry points (lt.h); every one returns int
 PROTOTYPES = {
+    "lt_set_labels": [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_int],
+    "lt_labels_info": [C.c_void_p, C.POINTER(C.c_int)],
+    "lt_tally_label_sums": [C.c_void_p, _DP, _U64P, _U64P, _U64P, _DP, C.POINTER(C.c_int64)],
+    "lt_tally_histogram": [C.c_void_p, _DP, C.c_int, _U64P, _DP, _U64P],
     "lt_tally_box": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _DP, _U64P],
     "lt_tally_convolve": [C.c_void_p, _DP, C.c_int, C.c_int, C.c_int, C.c_int, _DP],
     "lt_tally_convolve_sep": [C.c_void_p, _DP, C.c_int, _DP, C.c_int, C.c_int, C.c_int, _DP],
@@ -284,6 +291,7 @@ class Context:
         self.device_id = device_id
         self._grid_shape = None
         self._tally = None
+        self._mesh = None
 
     # -- plumbing ---------------------------------------------------------
     def _ck(self, rc, what):
@@ -339,6 +347,7 @@ class Context:
             raise LtError("set_mesh: medium arrays must have one entry per triangle")
         self._ck(lib().lt_set_mesh(self._h, _dp(v), _ip(mf), _ip(mb), C.c_int(v.shape[0]), arr.ctypes.data_as(C.c_void_p), C.c_int(n)),
                  "lt_set_mesh")
+        self._mesh = (v.copy(), mf.copy(), mb.copy())      # host copy: photon_tracing.label_volume reads a hit's sides from it
 
     def set_grid(self, shape, origin, voxel, dtype="f64"):
         nx, ny, nz = (int(s) for s in shape)
@@ -598,6 +607,58 @@ class Context:
         vox = np.zeros(e.size + 2, dtype=np.uint64)
         out, rawbuf, rp = self._sum_buffers((e.size + 2,), raw)
         self._ck(lib().lt_stats_summary(self._h, _dp(e), int(e.size), vox.ctypes.data_as(_U64P), _dp(out), rp), "lt_stats_summary")
+        return vox, (rawbuf if raw else out)
+
+    # -- the tally by region: label volume, per-label totals, histograms (lt.h: lt_set_labels ...) -------------------------
+    def set_labels(self, labels, n_labels=None):
+        """The label volume of the grid: uint8 [nz, ny, nx], every voxel 0 .. n_labels - 1 or LABEL_NONE (255: left out of
+        everything); n_labels (1 .. 64) defaults to the largest label + 1.  None releases it: the whole grid is label 0 again.
+        set_grid drops the labels."""
+        if labels is None:
+            self._ck(lib().lt_set_labels(self._h, None, 0, 0), "lt_set_labels")
+            return
+        a = np.asarray(labels)
+        if a.dtype != np.uint8:
+            raise LtError("set_labels: expected a uint8 array, got %s" % a.dtype.name)
+        if self._grid_shape is not None and a.shape != self._grid_shape:
+            raise LtError("set_labels: expected shape (nz, ny, nx) = %s, got %s" % (self._grid_shape, a.shape))
+        a = np.ascontiguousarray(a)
+        if n_labels is None:
+            used = a[a != LABEL_NONE]
+            n_labels = int(used.max()) + 1 if used.size else 1
+        self._ck(lib().lt_set_labels(self._h, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.size, int(n_labels)), "lt_set_labels")
+
+    def labels_info(self):
+        """The n_labels in force, 0 when no labels are set."""
+        n = C.c_int()
+        self._ck(lib().lt_labels_info(self._h, C.byref(n)), "lt_labels_info")
+        return n.value
+
+    def tally_label_sums(self, raw=False):
+        """dict of arrays [n_labels] (one label without set_labels): weight (float64 sum of the label's voxels), voxels,
+        filled (non-zero voxels; uint64), peak (float64: the largest voxel), peak_index (int64: the lowest flat index (z * ny
+        + y) * nx + x that holds it; the first voxel of an all-zero label, -1 for a label without voxels) and, with raw=True
+        (u64 fixed-point tally only), raw: the exact uint64 sums."""
+        n = max(self.labels_info(), 1)
+        out, rawbuf, rp = self._sum_buffers((n,), raw)
+        vox, filled = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        peak, idx = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int64)
+        self._ck(lib().lt_tally_label_sums(self._h, _dp(out), rp, vox.ctypes.data_as(_U64P), filled.ctypes.data_as(_U64P), _dp(peak),
+                                           idx.ctypes.data_as(C.POINTER(C.c_int64))), "lt_tally_label_sums")
+        res = dict(weight=out, voxels=vox, filled=filled, peak=peak, peak_index=idx)
+        if raw:
+            res["raw"] = rawbuf
+        return res
+
+    def tally_histogram(self, edges, raw=False):
+        """(voxels uint64, weight) [n_labels, len(edges) + 1]: per label, class k = the voxels whose value (as weight) has k
+        of the ascending ``edges`` at or below it, and the sum of their values.  raw=True (u64 fixed-point tally only): weight
+        is the exact uint64 sums.  The cumulative histogram is voxels[:, ::-1].cumsum(1)[:, ::-1]."""
+        e = _f64(edges).reshape(-1)
+        n = max(self.labels_info(), 1)
+        vox = np.zeros((n, e.size + 1), dtype=np.uint64)
+        out, rawbuf, rp = self._sum_buffers((n, e.size + 1), raw)
+        self._ck(lib().lt_tally_histogram(self._h, _dp(e), int(e.size), vox.ctypes.data_as(_U64P), _dp(out), rp), "lt_tally_histogram")
         return vox, (rawbuf if raw else out)
 
     def read_counters(self):

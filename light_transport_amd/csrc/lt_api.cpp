@@ -143,6 +143,11 @@ struct lt_ctx {
     bool stats_on = false, grid_touched = false;
     uint64_t stats_batches = 0;
     void stats_off() { d_stat_prev.release(); d_stat_m2.release(); stats_on = false; stats_batches = 0; }
+    // label volume of the grid (lt_set_labels): one byte per voxel on the device, and per label its first voxel (-1: none)
+    DevBuf d_labels;
+    int n_labels = 0;
+    std::vector<int64_t> label_first;
+    void labels_off() { d_labels.release(); n_labels = 0; label_first.clear(); }
     // Experiment knobs (lt_set_tuning; -1 = built-in default).  The environment variable LT_<KEY IN CAPITALS> seeds each of
     // them ONCE, in lt_create: nothing in this library reads the environment after that.
     struct Knobs {
@@ -1077,7 +1082,7 @@ int lt_destroy(lt_ctx* c)
     c->d_scratch_in.release(); c->d_scratch_out.release(); c->d_scratch_aux.release();
     c->d_mats.release(); c->d_lights.release(); c->d_r0.release(); c->d_r1.release(); c->d_lc.release();
     c->d_img.release(); c->d_xy.release(); c->d_vtx.release(); c->d_vcnt.release(); c->d_clear.release();
-    c->d_job.release(); c->d_dmap.release(); c->d_dmeta.release(); c->stats_off();
+    c->d_job.release(); c->d_dmap.release(); c->d_dmeta.release(); c->stats_off(); c->labels_off();
     c->d_mcell.release(); c->d_mlist.release(); c->d_mcoarse.release(); c->d_links.release();
     for (int k = 1; k < kMaxLanes; k++) { c->d_gridx[k - 1].release(); if (c->lanes[k].stream) (void)hipStreamSynchronize(c->lanes[k].stream); }
     for (int k = 0; k < kMaxLanes; k++) {
@@ -1181,6 +1186,7 @@ int lt_set_grid(lt_ctx* c, int nx, int ny, int nz, const double origin[3], const
     if ((double)nx * ny * nz > 2147483647.0) return c->fail(LT_E_UNSUPPORTED, "lt_set_grid: more than 2^31-1 voxels");
     BIND(c);
     if (c->stats_on) { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->stats_off(); }     // the moments belonged to the old grid
+    if (c->n_labels) { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->labels_off(); }    // ... and so did the labels
     c->nx = nx; c->ny = ny; c->nz = nz; c->tally = tally_dtype;
     for (int k = 0; k < 3; k++) { c->origin[k] = origin[k]; c->voxel[k] = voxel[k]; }
     HIP_TRY(c, c->d_grid.ensure(c->n_vox() * c->grid_elem()));
@@ -1991,6 +1997,121 @@ int lt_stats_summary(lt_ctx* c, const double* edges, int n_edges, uint64_t* voxe
     if (raw_weight_out) HIP_TRY(c, hipMemcpyAsync(raw_weight_out, d_out + n_cls * 8, n_cls * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(voxels_out, d_out + n_cls * 16, n_cls * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return LT_OK;
+}
+
+// ---- the tally by region: label volume, per-label totals, histograms (kernels: lt_tallylabel.hip) ----
+int lt_set_labels(lt_ctx* c, const uint8_t* labels, size_t n_voxels, int n_labels)
+{
+    CHECK_CTX(c);
+    if (!c->have_grid) return c->fail(LT_E_STATE, "lt_set_labels: no grid");
+    BIND(c);
+    if (!labels) {
+        if (c->n_labels) HIP_TRY(c, hipStreamSynchronize(c->stream));      // a pass may still be reading them
+        c->labels_off();
+        return LT_OK;
+    }
+    if (n_voxels != c->n_vox()) return c->fail(LT_E_INVALID, "lt_set_labels: expected %zu voxels, got %zu", c->n_vox(), n_voxels);
+    if (n_labels < 1 || n_labels > kMaxLabels) return c->fail(LT_E_INVALID, "lt_set_labels: n_labels %d, need 1 .. %d", n_labels, kMaxLabels);
+    std::vector<int64_t> first((size_t)n_labels, -1);
+    for (size_t i = 0; i < n_voxels; i++) {
+        const unsigned v = labels[i];
+        if (v == LT_LABEL_NONE) continue;
+        if (v >= (unsigned)n_labels)
+            return c->fail(LT_E_INVALID, "lt_set_labels: voxel %zu has label %u, neither below n_labels = %d nor LT_LABEL_NONE", i, v, n_labels);
+        if (first[v] < 0) first[v] = (int64_t)i;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (growing the buffer frees the old one)
+    if (c->d_labels.ensure(n_voxels) != hipSuccess) {
+        (void)hipGetLastError();
+        c->labels_off();
+        return c->fail(LT_E_NOMEM, "lt_set_labels: no device memory for %zu bytes", n_voxels);
+    }
+    c->n_labels = 0;
+    HIP_TRY(c, hipMemcpyAsync(c->d_labels.p, labels, n_voxels, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->n_labels = n_labels;
+    c->label_first.swap(first);
+    return LT_OK;
+}
+
+int lt_labels_info(lt_ctx* c, int* n_labels_out)
+{
+    CHECK_CTX(c);
+    if (!n_labels_out) return c->fail(LT_E_INVALID, "lt_labels_info: null output");
+    *n_labels_out = c->n_labels;
+    return LT_OK;
+}
+
+namespace {
+// the pass both results share; leaves the device results at the start of d_scratch_out (layout: launch_tally_label_bins)
+int label_pass(lt_ctx* c, const double* edges, int n_edges, int want_peak)
+{
+    const int L = c->n_labels ? c->n_labels : 1;
+    HIP_TRY(c, c->d_scratch_in.ensure(tally_label_partial_bytes(c->n_vox(), c->tally, L, n_edges)));
+    HIP_TRY(c, c->d_scratch_out.ensure(tally_label_out_bytes(L, n_edges)));
+    HIP_TRY(c, launch_tally_label_bins(c->d_grid.p, c->n_labels ? (const uint8_t*)c->d_labels.p : nullptr, c->tally, c->n_vox(), L, edges,
+                                       n_edges, want_peak, c->d_scratch_in.p, (double*)c->d_scratch_out.p, c->stream));
+    return LT_OK;
+}
+}  // namespace
+
+int lt_tally_label_sums(lt_ctx* c, double* weight_out, uint64_t* raw_out, uint64_t* voxels_out, uint64_t* filled_out, double* peak_out,
+                        int64_t* peak_index_out)
+{
+    CHECK_CTX(c);
+    if (!c->have_grid) return c->fail(LT_E_STATE, "lt_tally_label_sums: no grid");
+    if (!weight_out || !voxels_out || !filled_out || !peak_out || !peak_index_out)
+        return c->fail(LT_E_INVALID, "lt_tally_label_sums: weight_out, voxels_out, filled_out, peak_out and peak_index_out are required");
+    if (raw_out && c->tally != LT_TALLY_U64FX) return c->fail(LT_E_INVALID, "lt_tally_label_sums: raw_out needs the LT_TALLY_U64FX tally");
+    BIND(c);
+    int rc = label_pass(c, nullptr, 0, 1);
+    if (rc) return rc;
+    const size_t L = c->n_labels ? (size_t)c->n_labels : 1;
+    std::vector<uint64_t> h(6 * L);      // weight, raw, filled, zero, peak bits, peak index (32-bit, packed)
+    HIP_TRY(c, hipMemcpyAsync(h.data(), c->d_scratch_out.p, 6 * L * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint32_t* idx = (const uint32_t*)&h[5 * L];
+    for (size_t l = 0; l < L; l++) {
+        std::memcpy(&weight_out[l], &h[l], 8);
+        if (raw_out) raw_out[l] = h[L + l];
+        filled_out[l] = h[2 * L + l];
+        voxels_out[l] = h[2 * L + l] + h[3 * L + l];
+        const uint64_t bits = h[4 * L + l];
+        if (c->tally == LT_TALLY_U64FX) peak_out[l] = (double)bits * (1.0 / LT_FX_SCALE);
+        else if (c->tally == LT_TALLY_F64) std::memcpy(&peak_out[l], &bits, 8);
+        else { const uint32_t b32 = (uint32_t)bits; float f; std::memcpy(&f, &b32, 4); peak_out[l] = (double)f; }
+        if (voxels_out[l] == 0) peak_index_out[l] = -1;
+        else if (bits == 0) peak_index_out[l] = c->n_labels ? c->label_first[l] : 0;      // every voxel holds the peak: the first one
+        else peak_index_out[l] = (int64_t)idx[l];
+    }
+    return LT_OK;
+}
+
+int lt_tally_histogram(lt_ctx* c, const double* edges, int n_edges, uint64_t* voxels_out, double* weight_out, uint64_t* raw_weight_out)
+{
+    CHECK_CTX(c);
+    if (!c->have_grid) return c->fail(LT_E_STATE, "lt_tally_histogram: no grid");
+    if (!edges || !voxels_out || !weight_out) return c->fail(LT_E_INVALID, "lt_tally_histogram: edges, voxels_out and weight_out are required");
+    if (raw_weight_out && c->tally != LT_TALLY_U64FX) return c->fail(LT_E_INVALID, "lt_tally_histogram: raw_weight_out needs the LT_TALLY_U64FX tally");
+    if (n_edges < 1) return c->fail(LT_E_INVALID, "lt_tally_histogram: need at least one edge");
+    if (n_edges > kMaxStatEdges) return c->fail(LT_E_UNSUPPORTED, "lt_tally_histogram: %d edges, at most %d (the classes are counted in LDS)", n_edges, kMaxStatEdges);
+    for (int i = 0; i < n_edges; i++)
+        if (!std::isfinite(edges[i]) || edges[i] < 0.0 || (i > 0 && !(edges[i] > edges[i - 1])))
+            return c->fail(LT_E_INVALID, "lt_tally_histogram: edges must be finite, >= 0 and strictly ascending (edge %d)", i);
+    BIND(c);
+    int rc = label_pass(c, edges, n_edges, 0);
+    if (rc) return rc;
+    const size_t L = c->n_labels ? (size_t)c->n_labels : 1, n_cls = (size_t)n_edges + 1, bins = L * n_cls;
+    char* d_out = (char*)c->d_scratch_out.p;
+    std::vector<uint64_t> zero(L);
+    HIP_TRY(c, hipMemcpyAsync(weight_out, d_out, bins * 8, hipMemcpyDeviceToHost, c->stream));
+    if (raw_weight_out) HIP_TRY(c, hipMemcpyAsync(raw_weight_out, d_out + bins * 8, bins * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(voxels_out, d_out + bins * 16, bins * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(zero.data(), d_out + bins * 24, L * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t zero_cls = edges[0] == 0.0 ? 1 : 0;      // the class of the value 0: the number of edges <= 0
+    for (size_t l = 0; l < L; l++) voxels_out[l * n_cls + zero_cls] += zero[l];
     return LT_OK;
 }
 

@@ -1,6 +1,6 @@
 // lt_internal.hpp -- layouts and launcher declarations shared by the host API (lt_api.cpp, g++) and the gfx950 kernel
 // files (hipcc): lt_walk.hip, lt_query.hip, lt_render.hip (on the __device__ functions of lt_device.hpp) and lt_logtally.hip,
-// lt_tallysum.hip, lt_tallystats.hip, lt_tallyconv.hip (with lt_walk.hip on lt_tally.hpp); DESIGN.md section 1.  Not part of the public ABI.
+// lt_tallysum.hip, lt_tallystats.hip, lt_tallyconv.hip, lt_tallylabel.hip (with lt_walk.hip on lt_tally.hpp); DESIGN.md section 1.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -397,5 +397,19 @@ hipError_t launch_tally_convolve_at(const void* grid, int tally, int nx, int ny,
 // is u64 fixed point) the integer sums.  No partial sums: nothing but out and raw is written.
 hipError_t launch_tally_box(const void* grid, int tally, int nx, int ny, const int32_t lo[3], const int32_t size[3], const int32_t bin[3],
                             double* out, unsigned long long* raw, hipStream_t s);
+
+// The tally by region (lt_tallylabel.hip): every voxel booked under (label, class of its own value).  labels: device copy of
+// the label volume, one byte per voxel (0 .. n_labels - 1; anything else: left out), or null = label 0 everywhere.  edges: host
+// array, checked by the caller as for the statistics; n_edges 0 .. kMaxStatEdges (0: one class).  partials:
+// tally_label_partial_bytes(...); out: tally_label_out_bytes(...), 8-byte words with bins = n_labels * (n_edges + 1): weight f64
+// [bins], raw weight u64 [bins] (u64 fixed point only), NON-ZERO voxels u64 [bins], zero voxels u64 [n_labels] and, with
+// want_peak, the bits of the largest element u64 [n_labels] (a float's in the low bits) and the lowest flat index that holds it
+// u32 [n_labels] -- 0xffffffff for a label whose peak is 0: the caller knows its first voxel.
+constexpr int kMaxLabels = 64;
+uint32_t tally_label_parts(size_t n_vox, int tally);
+size_t tally_label_partial_bytes(size_t n_vox, int tally, int n_labels, int n_edges);
+size_t tally_label_out_bytes(int n_labels, int n_edges);
+hipError_t launch_tally_label_bins(const void* grid, const uint8_t* labels, int tally, size_t n, int n_labels, const double* edges,
+                                   int n_edges, int want_peak, void* partials, double* out, hipStream_t s);
 
 }  // namespace ltk

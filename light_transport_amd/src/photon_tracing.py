@@ -110,6 +110,68 @@ def block_lengths(size, bin):
     return np.minimum(start + bin, size) - start
 
 
+# label_volume sends one ray per voxel centre along this direction and reads the centre's medium off the nearest hit.  Near (0.3,
+# 0.5, 0.81): parallel to no axis, no face diagonal and no space diagonal.  The components are (1 / pi, 1 / 2, 1 / sqrt(1.5)), whose
+# ratios are irrational: voxel centres and mesh vertices usually sit on one rational lattice, and with a rational direction such
+# as (0.3, 0.5, 0.81) itself whole families of rays meet a wall exactly ON the diagonal its two triangles share, where neither
+# counts as hit (43 of 110 592 centres of the sphere-in-a-box scene came back without a hit that way).
+LABEL_RAY_DIRECTION = np.array([1.0 / np.pi, 0.5, 1.0 / np.sqrt(1.5)]) / np.linalg.norm([1.0 / np.pi, 0.5, 1.0 / np.sqrt(1.5)])
+LABEL_RAY_CHUNK = 1 << 22        # rays per intersect_rays call
+
+
+def voxel_centres(grid, axis):
+    """float64 [n]: the centres of the grid's voxels along axis 0 = x, 1 = y, 2 = z."""
+    return grid.origin[axis] + grid.voxel[axis] * (np.arange(grid.shape[axis], dtype=np.float64) + 0.5)
+
+
+def label_volume(ctx, geometry, grid):
+    """uint8 [nz, ny, nx]: the medium every voxel CENTRE lies in, as Context.set_labels takes it.
+
+    LayeredSlab (pure NumPy, ``ctx`` is not used): the layer k with z_bounds[k] <= z < z_bounds[k + 1] for the centre's z;
+    LABEL_NONE (255) for centres outside every layer.  Labels 0 .. len(media) - 1.
+
+    MeshVolume (the mesh has to be set on ``ctx``): one ray per voxel centre along LABEL_RAY_DIRECTION through
+    Context.intersect_rays; the nearest hit decides by the walk's own rule -- with n the triangle's normal (ab x ac) and d
+    the direction, d . n > 0 means the centre lies on the back side: med_back, otherwise med_front.  Medium m becomes label m;
+    the exterior (-1) and rays that hit nothing become label len(media), "outside": len(media) + 1 labels.
+
+    Two limits: the mesh has to be closed and consistently labelled (both sides of every surface name the media that really lie
+    there), or the nearest hit says nothing about the centre; and a voxel is classified by its centre alone -- a voxel the
+    surface cuts through belongs wholly to one side."""
+    nx, ny, nz = grid.shape
+    if isinstance(geometry, LayeredSlab):
+        zb = np.asarray(geometry.z_bounds, dtype=np.float64)
+        k = np.searchsorted(zb, voxel_centres(grid, 2), side="right") - 1
+        lab = np.where((k >= 0) & (k < len(geometry.media)), k, _lib.LABEL_NONE).astype(np.uint8)
+        return np.ascontiguousarray(np.broadcast_to(lab[:, None, None], (nz, ny, nx)))
+    if not isinstance(geometry, MeshVolume):
+        raise TypeError("label_volume: geometry must be a LayeredSlab or a MeshVolume")
+    mesh = getattr(ctx, "_mesh", None)
+    if mesh is None:
+        raise ValueError("label_volume: set the mesh on the context first (PhotonTracer.configure or Context.set_mesh)")
+    verts, med_front, med_back = mesh
+    n_media = len(geometry.media)
+    if n_media + 1 > _lib.MAX_LABELS:
+        raise ValueError("label_volume: %d media and the outside are more than %d labels" % (n_media, _lib.MAX_LABELS))
+    normal = np.cross(verts[:, 1] - verts[:, 0], verts[:, 2] - verts[:, 0])
+    back = normal @ LABEL_RAY_DIRECTION > 0.0            # per triangle: a ray along the direction meets it from behind
+    side = np.where(back, med_back, med_front)
+    out = np.empty(nx * ny * nz, dtype=np.uint8)
+    xs, ys, zs = (voxel_centres(grid, a) for a in range(3))
+    planes = max(1, LABEL_RAY_CHUNK // (nx * ny))
+    for z0 in range(0, nz, planes):
+        z1 = min(nz, z0 + planes)
+        o = np.empty((z1 - z0, ny, nx, 3))
+        o[..., 0], o[..., 1], o[..., 2] = xs[None, None, :], ys[None, :, None], zs[z0:z1, None, None]
+        o = o.reshape(-1, 3)
+        for r0 in range(0, o.shape[0], LABEL_RAY_CHUNK):         # (a single plane above the chunk size)
+            part = o[r0:r0 + LABEL_RAY_CHUNK]
+            prim, _ = ctx.intersect_rays(part, np.broadcast_to(LABEL_RAY_DIRECTION, part.shape))
+            med = np.where(prim >= 0, side[np.maximum(prim, 0)], -1)
+            out[z0 * ny * nx + r0:z0 * ny * nx + r0 + part.shape[0]] = np.where(med >= 0, med, n_media)
+    return out.reshape(nz, ny, nx)
+
+
 DEFAULT_MAX_STEPS = 1000000      # lt.h: the walk's hard cap (SURVEY Appendix C.8)
 
 
@@ -125,6 +187,7 @@ class PhotonTracer:
         self.photons = 0          # traced since the last reset (the fluence normalisation)
         self._profiles = {}       # run_batches: keep mask -> [batches, sum of the per-batch sums, sum of their squares]
         self._regions = {}        # run_batches: (lo, size, bin) -> the same moments of a binned box
+        self._label_moments = {}  # run_batches: "labels" -> the same moments of the per-label totals
 
     def configure(self, geometry, grid, source, primitives=None, linear_bvh=None, max_steps=None, quantity="absorbed"):
         ctx = self.ctx
@@ -160,7 +223,7 @@ class PhotonTracer:
         ctx.set_tally_quantity(quantity)     # "absorbed": weight absorbed per voxel; "fluence": w / mu_t per interaction
         self.grid, self.quantity, self.photons = grid, quantity, 0
         self.geometry, self.source = geometry, source
-        self._profiles, self._regions = {}, {}
+        self._profiles, self._regions, self._label_moments = {}, {}, {}
         return self
 
     def run(self, n_photons, seed=0, photon_offset=0, rng_table=None, f32_walk=False, wait=True):
@@ -170,14 +233,16 @@ class PhotonTracer:
             self.ctx.sync()
         return self
 
-    def run_batches(self, n_photons, n_batches, seed=0, photon_offset=0, f32_walk=False, profiles=(), regions=()):
+    def run_batches(self, n_photons, n_batches, seed=0, photon_offset=0, f32_walk=False, profiles=(), regions=(), labels=False):
         """``n_photons`` traced as ``n_batches`` consecutive id ranges of equal size, every one closed with a fold of the batch
         statistics (turned on here if they are off): the grid ends as run(n_photons) leaves it, and relative_error() /
         error_summary() say how far every voxel can be trusted.  ``profiles``: keep-strings as tally_sum takes them ("z": the
         depth profile); for each, the device sum is taken after every fold and the moments of the per-batch differences are
         kept on the host for profile_error() -- voxels of one batch are correlated, so the error of a sum does not follow
         from the per-voxel moments.  ``regions``: (lo, size, bin) triples as region() takes them; each box is read after every
-        fold in the same way, for region_error() -- the error of coarse voxels."""
+        fold in the same way, for region_error() -- the error of coarse voxels.  ``labels``: the per-label totals
+        (Context.tally_label_sums, by the label volume of set_regions) are taken after every fold too, for
+        region_totals_error()."""
         n_photons, n_batches = int(n_photons), int(n_batches)
         if n_batches < 2 or n_photons % n_batches:
             raise ValueError("run_batches: n_batches = %d must be at least 2 and divide n_photons = %d (equal batches)" % (n_batches, n_photons))
@@ -186,10 +251,13 @@ class PhotonTracer:
         # what is summed after every fold: (the moments' dict, its key, the device sum)
         sums = [(self._profiles, m, lambda m=m: ctx.tally_sum(m, raw=raw)) for m in (_lib.keep_mask(k) for k in profiles)]
         sums += [(self._regions, r, lambda r=r: ctx.tally_box(*r, raw=raw)) for r in (_box_key(*r) for r in regions)]
+        if labels:
+            sums.append((self._label_moments, "labels", lambda: ctx.tally_label_sums(raw=raw)["raw" if raw else "weight"]))
         if not ctx.stats_enabled():
             ctx.stats_enable(True)
             self._profiles.clear()
             self._regions.clear()
+            self._label_moments.clear()
         last = []
         for moments, key, read in sums:      # where a sum stands before the first batch (zero, unless earlier batches were run)
             last.append(read())
@@ -242,7 +310,7 @@ class PhotonTracer:
     def reset(self):
         self.ctx.zero_tally()
         self.photons = 0
-        self._profiles, self._regions = {}, {}
+        self._profiles, self._regions, self._label_moments = {}, {}, {}
 
     def absorbed(self):
         """float64 [nz, ny, nx]: absorbed photon weight per voxel (configure(..., quantity="absorbed"))."""
@@ -330,6 +398,61 @@ class PhotonTracer:
         """The whole grid at ``bin`` (an int, or (bx, by, bz)) times the voxel size: [ceil(nz / bz), ceil(ny / by), ceil(nx /
         bx)], the last voxel of an axis smaller where bin does not divide it (region)."""
         return self.region((0, 0, 0), self.grid.shape, bin if np.ndim(bin) else (bin,) * 3)[0]
+
+    # -- results by region: a label volume, per-label totals and dose-volume histograms (Context.tally_label_sums) ---------
+    def set_regions(self, labels=None):
+        """Give every voxel a region.  Default: label_volume of the configured geometry -- the medium of every voxel centre (a
+        mesh adds the label len(media), "outside").  An array uint8 [nz, ny, nx] (0 .. 63, or 255 to leave a voxel out) is taken
+        as given.  configure() sets a new grid, which drops the labels.  Returns the label volume."""
+        if labels is None:
+            labels = label_volume(self.ctx, self.geometry, self.grid)
+            n = len(self.geometry.media) + (1 if isinstance(self.geometry, MeshVolume) else 0)
+            self.ctx.set_labels(labels, n)
+        else:
+            labels = np.asarray(labels)
+            self.ctx.set_labels(labels)
+        return labels
+
+    def region_totals(self):
+        """dict of arrays, one entry per label (the whole grid as label 0 without set_regions), taken on the device:
+        ``weight`` the label's summed tally; ``share`` = weight / photons, the share of a launched photon's weight that went
+        into it; ``total`` the sum in the units of absorbed(), or the mean fluence over the label's voxels; ``voxels`` and
+        ``filled`` (non-zero voxels); ``peak`` its largest voxel in the units of absorbed() / fluence(); ``peak_index`` the lowest
+        flat index that holds it (-1: the label has no voxel) and ``peak_position`` [n, 3] = (x, y, z) of that voxel's centre in
+        scene units (NaN without a voxel)."""
+        r = self.ctx.tally_label_sums()
+        nx, ny, _ = self.grid.shape
+        idx = r["peak_index"]
+        cell = np.stack([idx % nx, (idx // nx) % ny, idx // (nx * ny)], axis=1).astype(np.float64)
+        pos = np.asarray(self.grid.origin) + np.asarray(self.grid.voxel) * (cell + 0.5)
+        pos[idx < 0] = np.nan
+        share = r["weight"] / float(self.photons) if self.photons > 0 else np.full(idx.shape, np.nan)
+        return dict(weight=r["weight"], share=share, total=self._normalised(r["weight"], r["voxels"]), voxels=r["voxels"],
+                    filled=r["filled"], peak=self._normalised(r["peak"], 1), peak_index=idx, peak_position=pos)
+
+    def dose_volume(self, edges):
+        """dict(volume=..., weight=...), float64 [n_labels, len(edges)] each: per label the fraction of its voxels, and of its
+        weight, in voxels AT OR ABOVE every edge -- the cumulative dose-volume histogram, from Context.tally_histogram.
+        ``edges``: ascending, in the units of absorbed() / fluence().  NaN for a label without voxels (or without weight)."""
+        e = np.asarray(edges, dtype=np.float64).reshape(-1)
+        if self.quantity == "fluence":
+            if self.photons <= 0:
+                raise ValueError("nothing traced since the last reset")
+            e = e * (self.grid.voxel_volume * float(self.photons))        # a voxel's fluence -> its weight
+        vox, w = self.ctx.tally_histogram(e)
+        above_v = vox[:, ::-1].cumsum(axis=1)[:, ::-1].astype(np.float64)
+        above_w = w[:, ::-1].cumsum(axis=1)[:, ::-1]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return dict(volume=above_v[:, 1:] / np.where(above_v[:, :1] > 0, above_v[:, :1], np.nan),
+                        weight=above_w[:, 1:] / np.where(above_w[:, :1] > 0, above_w[:, :1], np.nan))
+
+    def region_totals_error(self):
+        """The relative standard error of every label's total over the batches of run_batches(..., labels=True):
+        _lib.relative_error(batches, sum, sum of squares) of the per-batch label totals."""
+        if "labels" not in self._label_moments:
+            raise ValueError("region_totals_error(): run_batches(..., labels=True) first")
+        n, s1, s2 = self._label_moments["labels"]
+        return _lib.relative_error(n, s1, s2)
 
     # -- the response to a beam of finite width: the tally convolved in x and y on the device ------------------------
     def _beam_column(self, who):
