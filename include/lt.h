@@ -440,6 +440,46 @@ int lt_tally_label_sums(lt_ctx* ctx, double* weight_out, uint64_t* raw_out, uint
 int lt_tally_histogram(lt_ctx* ctx, const double* edges, int n_edges, uint64_t* voxels_out, double* weight_out,
                        uint64_t* raw_weight_out);
 
+/* ---- the tally along rays: line integrals, maxima, the first voxel above a threshold ------ */
+/* Everything above is locked to the grid's axes.  These two calls read the tally along ARBITRARY rays -- an oblique projection,
+ * the integral along a tilted fibre, a maximum-intensity projection, "how deep does the 10 % isodose reach, seen from here" --
+ * and return a few numbers per ray; the grid stays on the device.  One lane per ray steps voxel to voxel through the grid.
+ *   W[v]         the voxel as weight, converted exactly as lt_read_grid_f64 converts it.
+ *   voxel boxes  voxel (i, j, k) is the half-open box [origin_a + i voxel_a, origin_a + (i + 1) voxel_a) on every axis: the walk's
+ *                floor rule.
+ *   rays         o + t d for t_lo <= t <= t_hi; d of any non-zero finite length; lengths are geometric, (t2 - t1) |d|.
+ *   integral     sum over the voxels v of W[v] l_v, with l_v the length of the ray's segment inside v: weight x length.
+ *   max          the largest W among the voxels with l_v > 0 (LT_TALLY_U64FX: the integers are compared, the largest converted
+ *                once); max_index the flat index (z ny + y) nx + x of the FIRST such voxel along the ray that holds it.  A ray that
+ *                crosses no voxel: max 0, index -1.
+ *   first        first_index: the first voxel along the ray with l_v > 0 and W >= threshold (the comparison is on the converted
+ *                double, as lt_tally_histogram classes a voxel); first_t: the parameter at which the ray enters it, never below
+ *                t_lo, in the units of the d given.  No such voxel: +inf and -1, as lt_intersect_rays reports a miss.  threshold =
+ *                0 therefore returns the entry into the grid.
+ *   d_a == 0     the index on that axis is floor((o_a - origin_a) / voxel_a) throughout; outside 0 .. n_a - 1 the ray misses.
+ *   grazing      whether a voxel that the ray only grazes -- a corner, an edge, a chord within rounding of zero -- is visited is
+ *                unspecified; what it adds to the integral is negligible either way.
+ * Arithmetic: f64 throughout, every operation rounded on its own (no fused multiply-add).  The parameter of a grid plane is the
+ * quotient ((origin_a + p voxel_a) - o_a) / d_a of the plane's own coordinate, never a repeated addition: the error does not grow
+ * with the grid.  No atomics; a ray is summed in the order it is walked: the same call on an unchanged grid returns identical
+ * bits, for all three tally types.
+ * Any output pointer may be NULL (at least one is not); only what is asked for is computed.  Both calls run on the ctx stream
+ * behind earlier launches (as lt_read_grid is ordered), block until the outputs are filled, and leave the grid, the counters, the
+ * statistics and the labels untouched.  Rays and outputs live in the ctx's scratch buffers.
+ * LT_E_STATE without a grid.  LT_E_INVALID, all checked on the host (lt_last_error names the first offending ray): no output asked
+ * for; a NULL origins, dirs, camera, xs or ys; n, width or height < 1; a non-finite origin or direction, or d = 0; t_lo < 0 or not
+ * finite, or t_hi <= t_lo (t_hi = +inf is legal); a first-crossing output with a threshold that is negative or not finite. */
+
+/* origins, dirs [n][3]; t_range [n][2] = (t_lo, t_hi) per ray, or NULL = [0, +inf); every output [n] */
+int lt_tally_rays(lt_ctx* ctx, const double* origins, const double* dirs, const double* t_range, size_t n, double threshold,
+                  double* integral_out, double* max_out, int64_t* max_index_out, double* first_t_out, int64_t* first_index_out);
+/* The rays of the pinhole camera of lt_render_surface, without its jitter: pixel (i, j) has o = camera and d = (xs[j] - o.x,
+ * ys[i] - o.y, f_distance - o.z), t in [0, +inf); every output [height][width].  The same __device__ traversal as lt_tally_rays:
+ * the result equals lt_tally_rays on those rays built on the host, bit for bit.  A wave takes an 8 x 8 pixel tile. */
+int lt_tally_view(lt_ctx* ctx, int width, int height, const double camera[3], double f_distance, const double* xs, const double* ys,
+                  double threshold, double* integral_out, double* max_out, int64_t* max_index_out, double* first_t_out,
+                  int64_t* first_index_out);
+
 int lt_grid_device_ptr(lt_ctx* ctx, void** ptr, size_t* bytes);
 int lt_counters_device_ptr(lt_ctx* ctx, void** ptr, size_t* bytes);
 void* lt_stream(lt_ctx* ctx); /* hipStream_t of the ctx */

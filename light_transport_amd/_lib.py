@@ -38,11 +38,15 @@ SYMBOLS = [
     "lt_stats_enable", "lt_stats_fold", "lt_stats_batches", "lt_stats_read_m2", "lt_stats_read_relerr", "lt_stats_summary",
     "lt_tally_convolve", "lt_tally_convolve_sep", "lt_tally_convolve_at", "lt_tally_box",
     "lt_set_labels", "lt_labels_info", "lt_tally_label_sums", "lt_tally_histogram",
+    "lt_tally_rays", "lt_tally_view",
 ]
 _U64P = C.POINTER(C.c_uint64)
 _DP = C.POINTER(C.c_double)
-# prototypes of the lt_stats_*, lt_tally_convolve*, lt_tally_box and label entry points (lt.h); every one returns int
+_I64P = C.POINTER(C.c_int64)
+# prototypes of the lt_stats_*, lt_tally_convolve*, lt_tally_box, label and ray entry points (lt.h); every one returns int
 PROTOTYPES = {
+    "lt_tally_rays": [C.c_void_p, _DP, _DP, _DP, C.c_size_t, C.c_double, _DP, _DP, _I64P, _DP, _I64P],
+    "lt_tally_view": [C.c_void_p, C.c_int, C.c_int, _DP, C.c_double, _DP, _DP, C.c_double, _DP, _DP, _I64P, _DP, _I64P],
     "lt_set_labels": [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_int],
     "lt_labels_info": [C.c_void_p, C.POINTER(C.c_int)],
     "lt_tally_label_sums": [C.c_void_p, _DP, _U64P, _U64P, _U64P, _DP, C.POINTER(C.c_int64)],
@@ -173,6 +177,29 @@ def relative_error(n, s1, m2):
         v = np.where(v < 0.0, 0.0, v)
         r = np.sqrt(v / (n - 1.0))
     return np.where(s1 == 0.0, np.nan, r)
+
+
+RAY_WANTS = ("integral", "max", "first")
+
+
+def ray_wants(want):
+    """``want`` of tally_rays / tally_view as a tuple out of RAY_WANTS, in that order: one name or several, at least one."""
+    names = (want,) if isinstance(want, str) else tuple(want)
+    if not names or any(w not in RAY_WANTS for w in names):
+        raise ValueError("want=%r: one or more of %s" % (want, ", ".join(RAY_WANTS)))
+    return tuple(w for w in RAY_WANTS if w in names)
+
+
+def camera_rays(camera, f_distance, xs, ys):
+    """(origins, dirs) float64 [H, W, 3]: the rays of lt_tally_view built on the host -- pixel (i, j) starts at the camera with
+    d = (xs[j] - o.x, ys[i] - o.y, f_distance - o.z), the primary ray of lt_render_surface without its jitter."""
+    o = _f64(np.asarray(camera, dtype=np.float64).ravel()[:3])
+    xs, ys = _f64(xs).reshape(-1), _f64(ys).reshape(-1)
+    d = np.empty((ys.size, xs.size, 3), dtype=np.float64)
+    d[..., 0] = (xs - o[0])[None, :]
+    d[..., 1] = (ys - o[1])[:, None]
+    d[..., 2] = np.float64(f_distance) - o[2]
+    return np.ascontiguousarray(np.broadcast_to(o, d.shape)), d
 
 
 class Medium(C.Structure):
@@ -660,6 +687,46 @@ class Context:
         out, rawbuf, rp = self._sum_buffers((n, e.size + 1), raw)
         self._ck(lib().lt_tally_histogram(self._h, _dp(e), int(e.size), vox.ctypes.data_as(_U64P), _dp(out), rp), "lt_tally_histogram")
         return vox, (rawbuf if raw else out)
+
+    # -- the tally along rays (lt.h: lt_tally_rays, lt_tally_view) ---------------------------------------------------------
+    def _ray_buffers(self, shape, want, threshold):
+        """(dict of output arrays of ``shape``, the five ctypes pointers in lt.h's order, threshold as a float)."""
+        names = ray_wants(want)
+        res, ptr = {}, []
+        for key, group, dt in (("integral", "integral", np.float64), ("max", "max", np.float64), ("max_index", "max", np.int64),
+                               ("first_t", "first", np.float64), ("first_index", "first", np.int64)):
+            if group in names:
+                res[key] = np.empty(shape, dtype=dt)
+                ptr.append(res[key].ctypes.data_as(_DP if dt is np.float64 else _I64P))
+            else:
+                ptr.append(None)
+        return res, ptr, 0.0 if threshold is None else float(threshold)
+
+    def tally_rays(self, origins, dirs, t_range=None, threshold=None, want=RAY_WANTS):
+        """The tally along rays o + t d (origins, dirs: float64 [n, 3]; t_range: [n, 2] = (t_lo, t_hi) per ray, one pair for all,
+        or None = [0, inf)), walked voxel by voxel on the device.  A dict of arrays [n], by ``want``: "integral" -> integral (sum
+        of voxel weight x length of the ray inside the voxel); "max" -> max (the largest voxel on the ray, as weight) and
+        max_index (the flat index (z ny + y) nx + x of the first voxel along the ray that holds it, -1 for a ray that crosses no
+        voxel); "first" -> first_index (the first voxel along the ray whose weight is >= ``threshold``) and first_t (the
+        parameter at which the ray enters it; inf and -1 without one).  threshold=None is 0: the entry into the grid."""
+        o, d = _f64(origins).reshape(-1, 3), _f64(dirs).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise LtError("tally_rays: %d origins and %d directions" % (n, d.shape[0]))
+        tr = None if t_range is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_range, dtype=np.float64), (n, 2)))
+        res, p, thr = self._ray_buffers((n,), want, threshold)
+        self._ck(lib().lt_tally_rays(self._h, _dp(o), _dp(d), _dp(tr), C.c_size_t(n), C.c_double(thr), *p), "lt_tally_rays")
+        return res
+
+    def tally_view(self, camera, f_distance, xs, ys, threshold=None, want=RAY_WANTS):
+        """tally_rays along the rays of render_surface's pinhole camera (camera_rays), built on the device: a dict of arrays
+        [len(ys), len(xs)], bit for bit what tally_rays returns for those rays."""
+        cam = (C.c_double * 3)(*[float(x) for x in np.asarray(camera).ravel()[:3]])
+        xs, ys = _f64(xs).reshape(-1), _f64(ys).reshape(-1)
+        res, p, thr = self._ray_buffers((ys.size, xs.size), want, threshold)
+        self._ck(lib().lt_tally_view(self._h, C.c_int(xs.size), C.c_int(ys.size), cam, C.c_double(float(f_distance)), _dp(xs), _dp(ys),
+                                     C.c_double(thr), *p), "lt_tally_view")
+        return res
 
     def read_counters(self):
         c = Counters()

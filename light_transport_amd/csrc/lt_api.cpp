@@ -2115,6 +2115,134 @@ int lt_tally_histogram(lt_ctx* c, const double* edges, int n_edges, uint64_t* vo
     return LT_OK;
 }
 
+// ---- the tally along rays (kernels: lt_tallyrays.hip) -----------------------
+namespace {
+// what both calls share.  The outputs of n rays lie in d_scratch_out as five blocks of n 8-byte words, in the order of the
+// arguments; a block nobody asked for is neither written nor copied.
+struct RayOutputs { double* integral; double* max_w; int64_t* max_index; double* first_t; int64_t* first_index; };
+
+int ray_outputs_ok(lt_ctx* c, const char* who, const RayOutputs& h, double threshold)
+{
+    if (!c->have_grid) return c->fail(LT_E_STATE, "%s: no grid", who);
+    if (!h.integral && !h.max_w && !h.max_index && !h.first_t && !h.first_index) return c->fail(LT_E_INVALID, "%s: no output asked for", who);
+    if ((h.first_t || h.first_index) && !(std::isfinite(threshold) && threshold >= 0.0))
+        return c->fail(LT_E_INVALID, "%s: threshold %g, a first-crossing output needs a finite threshold >= 0", who, threshold);
+    return LT_OK;
+}
+TallyRayGrid ray_grid_of(const lt_ctx* c)
+{
+    TallyRayGrid g;
+    g.n[0] = c->nx; g.n[1] = c->ny; g.n[2] = c->nz;
+    for (int a = 0; a < 3; a++) { g.origin[a] = c->origin[a]; g.voxel[a] = c->voxel[a]; }
+    return g;
+}
+int ray_device_outputs(lt_ctx* c, size_t n, const RayOutputs& h, TallyRayOut* d)
+{
+    HIP_TRY(c, c->d_scratch_out.ensure(n * 40));
+    char* base = (char*)c->d_scratch_out.p;
+    d->integral = h.integral ? (double*)base : nullptr;
+    d->max_w = h.max_w ? (double*)(base + n * 8) : nullptr;
+    d->max_index = h.max_index ? (int64_t*)(base + n * 16) : nullptr;
+    d->first_t = h.first_t ? (double*)(base + n * 24) : nullptr;
+    d->first_index = h.first_index ? (int64_t*)(base + n * 32) : nullptr;
+    return LT_OK;
+}
+int ray_read_back(lt_ctx* c, size_t n, const RayOutputs& h, const TallyRayOut& d)
+{
+    if (h.integral) HIP_TRY(c, hipMemcpyAsync(h.integral, d.integral, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h.max_w) HIP_TRY(c, hipMemcpyAsync(h.max_w, d.max_w, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h.max_index) HIP_TRY(c, hipMemcpyAsync(h.max_index, d.max_index, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h.first_t) HIP_TRY(c, hipMemcpyAsync(h.first_t, d.first_t, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (h.first_index) HIP_TRY(c, hipMemcpyAsync(h.first_index, d.first_index, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return LT_OK;
+}
+bool finite3(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+}  // namespace
+
+int lt_tally_rays(lt_ctx* c, const double* origins, const double* dirs, const double* t_range, size_t n, double threshold,
+                  double* integral_out, double* max_out, int64_t* max_index_out, double* first_t_out, int64_t* first_index_out)
+{
+    CHECK_CTX(c);
+    const char* who = "lt_tally_rays";
+    const RayOutputs h = {integral_out, max_out, max_index_out, first_t_out, first_index_out};
+    int rc = ray_outputs_ok(c, who, h, threshold);
+    if (rc) return rc;
+    if (!origins || !dirs) return c->fail(LT_E_INVALID, "%s: origins and dirs are required", who);
+    if (n < 1) return c->fail(LT_E_INVALID, "%s: n = 0, need at least one ray", who);
+    for (size_t r = 0; r < n; r++) {
+        const double* o = origins + 3 * r;
+        const double* d = dirs + 3 * r;
+        if (!finite3(o)) return c->fail(LT_E_INVALID, "%s: ray %zu has a non-finite origin (%g, %g, %g)", who, r, o[0], o[1], o[2]);
+        if (!finite3(d)) return c->fail(LT_E_INVALID, "%s: ray %zu has a non-finite direction (%g, %g, %g)", who, r, d[0], d[1], d[2]);
+        if (d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0) return c->fail(LT_E_INVALID, "%s: ray %zu has direction 0", who, r);
+        if (t_range) {
+            const double lo = t_range[2 * r], hi = t_range[2 * r + 1];
+            if (!std::isfinite(lo) || lo < 0.0) return c->fail(LT_E_INVALID, "%s: ray %zu has t_lo = %g, need a finite t_lo >= 0", who, r, lo);
+            if (!(hi > lo)) return c->fail(LT_E_INVALID, "%s: ray %zu has t_hi = %g, need t_hi > t_lo = %g", who, r, hi, lo);
+        }
+    }
+    BIND(c);
+    // layout of the staging buffer: origins | dirs | t_range
+    const size_t vb = n * 3 * sizeof(double), tb = n * 2 * sizeof(double);
+    HIP_TRY(c, c->d_scratch_in.ensure(2 * vb + tb));
+    char* base = (char*)c->d_scratch_in.p;
+    HIP_TRY(c, hipMemcpyAsync(base, origins, vb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(base + vb, dirs, vb, hipMemcpyHostToDevice, c->stream));
+    if (t_range) HIP_TRY(c, hipMemcpyAsync(base + 2 * vb, t_range, tb, hipMemcpyHostToDevice, c->stream));
+    TallyRayOut d_out;
+    if ((rc = ray_device_outputs(c, n, h, &d_out))) return rc;
+    HIP_TRY(c, launch_tally_rays(c->d_grid.p, c->tally, ray_grid_of(c), (const double*)base, (const double*)(base + vb),
+                                 t_range ? (const double*)(base + 2 * vb) : nullptr, n, threshold, d_out, c->stream));
+    return ray_read_back(c, n, h, d_out);
+}
+
+int lt_tally_view(lt_ctx* c, int width, int height, const double camera[3], double f_distance, const double* xs, const double* ys,
+                  double threshold, double* integral_out, double* max_out, int64_t* max_index_out, double* first_t_out,
+                  int64_t* first_index_out)
+{
+    CHECK_CTX(c);
+    const char* who = "lt_tally_view";
+    const RayOutputs h = {integral_out, max_out, max_index_out, first_t_out, first_index_out};
+    int rc = ray_outputs_ok(c, who, h, threshold);
+    if (rc) return rc;
+    if (!camera || !xs || !ys) return c->fail(LT_E_INVALID, "%s: camera, xs and ys are required", who);
+    if (width < 1 || height < 1) return c->fail(LT_E_INVALID, "%s: %d x %d pixels, need at least 1 x 1", who, width, height);
+    if (height > 16 * 65535) return c->fail(LT_E_UNSUPPORTED, "%s: %d rows, at most %d", who, height, 16 * 65535);
+    if (!finite3(camera)) return c->fail(LT_E_INVALID, "%s: non-finite camera (%g, %g, %g): ray 0", who, camera[0], camera[1], camera[2]);
+    // a pixel's direction is (xs[j] - o.x, ys[i] - o.y, f_distance - o.z): finite if its three terms are, zero if all three are
+    const double dz = f_distance - camera[2];
+    int j_bad = -1, i_bad = -1, j_zero = -1, i_zero = -1;
+    for (int j = width - 1; j >= 0; j--) {
+        const double v = xs[j] - camera[0];
+        if (!std::isfinite(v)) j_bad = j;
+        if (v == 0.0) j_zero = j;
+    }
+    for (int i = height - 1; i >= 0; i--) {
+        const double v = ys[i] - camera[1];
+        if (!std::isfinite(v)) i_bad = i;
+        if (v == 0.0) i_zero = i;
+    }
+    if (!std::isfinite(dz) || i_bad >= 0 || j_bad >= 0) {
+        int ii = 0, jj = 0;      // the first such pixel in row order: (0, 0) if every pixel or row 0 is bad, else the first bad column of row 0
+        if (std::isfinite(dz) && i_bad != 0) { if (j_bad >= 0) jj = j_bad; else ii = i_bad; }
+        return c->fail(LT_E_INVALID, "%s: ray %zu (pixel row %d, column %d) has a non-finite direction", who, (size_t)ii * width + jj, ii, jj);
+    }
+    if (dz == 0.0 && i_zero >= 0 && j_zero >= 0)
+        return c->fail(LT_E_INVALID, "%s: ray %zu (pixel row %d, column %d) has direction 0", who, (size_t)i_zero * width + j_zero, i_zero, j_zero);
+    BIND(c);
+    const size_t n = (size_t)width * (size_t)height;
+    HIP_TRY(c, c->d_scratch_in.ensure(((size_t)width + height) * sizeof(double)));
+    double* d_xs = (double*)c->d_scratch_in.p;
+    double* d_ys = d_xs + width;
+    HIP_TRY(c, hipMemcpyAsync(d_xs, xs, (size_t)width * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_ys, ys, (size_t)height * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    TallyRayOut d_out;
+    if ((rc = ray_device_outputs(c, n, h, &d_out))) return rc;
+    HIP_TRY(c, launch_tally_view(c->d_grid.p, c->tally, ray_grid_of(c), width, height, camera, f_distance, d_xs, d_ys, threshold, d_out, c->stream));
+    return ray_read_back(c, n, h, d_out);
+}
+
 int lt_radial_bins(int nx, int ny, const double origin_xy[2], const double voxel_xy[2], const double centre_xy[2], double dr, int nr,
                    int32_t* bins_out)
 {

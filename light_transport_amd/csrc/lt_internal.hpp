@@ -412,4 +412,16 @@ size_t tally_label_out_bytes(int n_labels, int n_edges);
 hipError_t launch_tally_label_bins(const void* grid, const uint8_t* labels, int tally, size_t n, int n_labels, const double* edges,
                                    int n_edges, int want_peak, void* partials, double* out, hipStream_t s);
 
+// The tally along rays (lt_tallyrays.hip).  Rays and camera are checked by the caller (finite, d != 0, 0 <= t_lo < t_hi); every
+// pointer is a device pointer.  o, d [n][3], t_range [n][2] or null = [0, +inf); xs [width], ys [height].  An output that is null is
+// not written; the kernel instantiated is the one for tally_ray_mask(out) (1 integral, 2 maximum, 4 first crossing; 1, 2, 4 and 7
+// exist, any other combination takes 7).
+struct TallyRayGrid { int n[3]; double origin[3], voxel[3]; };      // x, y, z order
+struct TallyRayOut { double* integral; double* max_w; int64_t* max_index; double* first_t; int64_t* first_index; };
+int tally_ray_mask(const TallyRayOut& out);
+hipError_t launch_tally_rays(const void* grid, int tally, const TallyRayGrid& g, const double* o, const double* d, const double* t_range,
+                             size_t n, double threshold, const TallyRayOut& out, hipStream_t s);
+hipError_t launch_tally_view(const void* grid, int tally, const TallyRayGrid& g, int width, int height, const double camera[3],
+                             double f_distance, const double* xs, const double* ys, double threshold, const TallyRayOut& out, hipStream_t s);
+
 }  // namespace ltk

@@ -454,6 +454,83 @@ class PhotonTracer:
         n, s1, s2 = self._label_moments["labels"]
         return _lib.relative_error(n, s1, s2)
 
+    # -- the tally along rays: through a camera, along a line, along any direction (Context.tally_rays / tally_view) --------
+    def _ray_quantity(self, what, threshold, call, dir_length):
+        """One of "integral", "max", "depth" from the device call ``call(want, threshold as weight)`` -> dict of arrays, in this
+        tracer's units.  integral: the tally's density integrated along the ray -- absorbed weight per volume x length, or
+        fluence per launched photon x length; max: the largest voxel on the ray in the units of absorbed() / fluence(); depth:
+        the geometric distance first_t x |d| from the ray's origin to where it enters the first voxel at or above ``threshold``
+        (in those same units), inf where there is none."""
+        if what not in ("integral", "max", "depth"):
+            raise ValueError("what=%r: 'integral', 'max' or 'depth'" % (what,))
+        if self.quantity == "fluence" and self.photons <= 0:
+            raise ValueError("nothing traced since the last reset")
+        per_voxel = self.grid.voxel_volume * (float(self.photons) if self.quantity == "fluence" else 1.0)
+        if what == "integral":
+            return call(("integral",), None)["integral"] / per_voxel
+        if what == "max":
+            return self._normalised(call(("max",), None)["max"], 1)
+        if threshold is None or not np.isfinite(threshold) or threshold < 0:
+            raise ValueError("what='depth' needs a finite threshold >= 0 in the units of absorbed() / fluence(), not %r" % (threshold,))
+        as_weight = float(threshold) * (per_voxel if self.quantity == "fluence" else 1.0)       # a voxel's fluence -> its weight
+        return call(("first",), as_weight)["first_t"] * dir_length
+
+    def view(self, scene, what="integral", threshold=None):
+        """float64 [H, W]: the tally seen through the camera of ``scene`` -- the pixel rays of render_scene (scene.camera[:3],
+        scene.f_distance, np.linspace(left, right, W), np.linspace(top, bottom, H)), without their jitter, walked through the
+        voxel grid on the device.  ``what``: "integral", "max" or "depth" (with ``threshold``), as _ray_quantity defines them."""
+        xs = np.linspace(scene.left, scene.right, scene.width)
+        ys = np.linspace(scene.top, scene.bottom, scene.height)
+        cam = np.asarray(scene.camera, dtype=np.float64).ravel()[:3]
+        length = np.linalg.norm(_lib.camera_rays(cam, scene.f_distance, xs, ys)[1], axis=-1)
+        return self._ray_quantity(what, threshold, lambda want, thr: self.ctx.tally_view(cam, scene.f_distance, xs, ys, threshold=thr, want=want),
+                                  length)
+
+    def line_integral(self, p0, p1):
+        """The tally's density integrated along the straight segment from ``p0`` to ``p1`` (a fibre, a biopsy track): a float in
+        the units of view(..., "integral")."""
+        p0, p1 = np.asarray(p0, dtype=np.float64).reshape(3), np.asarray(p1, dtype=np.float64).reshape(3)
+        if not (np.all(np.isfinite(p0)) and np.all(np.isfinite(p1))) or np.array_equal(p0, p1):
+            raise ValueError("line_integral: two distinct finite points, not %r and %r" % (p0.tolist(), p1.tolist()))
+        call = lambda want, thr: self.ctx.tally_rays(p0[None, :], (p1 - p0)[None, :], t_range=(0.0, 1.0), threshold=thr, want=want)   # noqa: E731
+        return float(self._ray_quantity("integral", None, call, 1.0)[0])
+
+    def parallel_rays(self, direction, centre, up, width, height, extent):
+        """(origins, dirs) float64 [height, width, 3] of parallel_projection: every ray runs along w = direction / |direction|.
+        The image plane passes through ``centre``; with v = ``up`` made orthogonal to w and u = w x v (to the right of a viewer
+        who looks along w with v up), pixel (i, j) sits at centre + a u + b v with a = ((j + 0.5) / width - 0.5) ew and b = (0.5 -
+        (i + 0.5) / height) eh -- row 0 at the top -- where ``extent`` = (ew, eh), or one number for both, is the size of the image
+        in scene units.  The rays start behind every corner of the grid."""
+        w, c, v = (np.asarray(a, dtype=np.float64).reshape(3) for a in (direction, centre, up))
+        width, height = int(width), int(height)
+        ew, eh = (float(e) for e in (extent if np.ndim(extent) else (extent, extent)))
+        if not np.all(np.isfinite(w)) or not np.any(w) or not np.all(np.isfinite(c)) or not np.all(np.isfinite(v)):
+            raise ValueError("parallel_projection: direction, centre and up must be finite and direction non-zero")
+        w = w / np.linalg.norm(w)
+        v = v - np.dot(v, w) * w
+        if not np.linalg.norm(v) > 1e-12 * max(np.linalg.norm(np.asarray(up, dtype=np.float64)), 1e-300):
+            raise ValueError("parallel_projection: up=%r is parallel to the direction" % (up,))
+        v = v / np.linalg.norm(v)
+        u = np.cross(w, v)
+        if width < 1 or height < 1 or not (ew > 0 and eh > 0 and np.isfinite(ew) and np.isfinite(eh)):
+            raise ValueError("parallel_projection: width, height >= 1 and a finite extent > 0")
+        lo = np.asarray(self.grid.origin)
+        hi = lo + np.asarray(self.grid.voxel) * np.asarray(self.grid.shape)
+        corners = np.array([[x, y, z] for x in (lo[0], hi[0]) for y in (lo[1], hi[1]) for z in (lo[2], hi[2])])
+        back = float(np.min((corners - c) @ w)) - float(np.linalg.norm(hi - lo))
+        a = ((np.arange(width) + 0.5) / width - 0.5) * ew
+        b = (0.5 - (np.arange(height) + 0.5) / height) * eh
+        o = c + a[None, :, None] * u + b[:, None, None] * v + back * w
+        return np.ascontiguousarray(o), np.ascontiguousarray(np.broadcast_to(w, o.shape))
+
+    def parallel_projection(self, direction, centre, up, width, height, extent, what="integral", threshold=None):
+        """float64 [height, width]: the orthographic view of the tally along ``direction`` -- any direction, where projection()
+        knows the three axes -- through the rays of parallel_rays; ``what`` as for view (a depth is measured from the rays'
+        start behind the grid)."""
+        o, d = self.parallel_rays(direction, centre, up, width, height, extent)
+        call = lambda want, thr: self.ctx.tally_rays(o.reshape(-1, 3), d.reshape(-1, 3), threshold=thr, want=want)   # noqa: E731
+        return self._ray_quantity(what, threshold, call, 1.0).reshape(o.shape[:2])
+
     # -- the response to a beam of finite width: the tally convolved in x and y on the device ------------------------
     def _beam_column(self, who):
         """(ix, iy) of the column whose centre the pencil enters through -- or ValueError: the convolution of the tally with a
