@@ -325,6 +325,7 @@ template <> struct Mx<double> {
     static LT_DEV double log(double x) { return ::log(x); }
     static LT_DEV double sqrt(double x) { return ::sqrt(x); }
     static LT_DEV double abs(double x) { return ::fabs(x); }
+    static LT_DEV double fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
     static LT_DEV double clamp_unit(double c) { return __builtin_fmax(__builtin_fmin(c, 1.0), -1.0); }
     static LT_DEV double sin(double x) { return ::sin(x); }
     static LT_DEV double cos(double x) { return ::cos(x); }
@@ -354,6 +355,7 @@ template <> struct Mx<float> {
     static LT_DEV float log(float x) { return ::logf(x); }
     static LT_DEV float sqrt(float x) { return ::sqrtf(x); }
     static LT_DEV float abs(float x) { return ::fabsf(x); }
+    static LT_DEV float fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
     static LT_DEV float clamp_unit(float c) { return __builtin_fmaxf(__builtin_fminf(c, 1.0f), -1.0f); }
     static LT_DEV float sin(float x) { return ::sinf(x); }
     static LT_DEV float cos(float x) { return ::cosf(x); }

@@ -57,11 +57,18 @@ template <int TALLY> LT_DEV void tally_add(void* grid, unsigned idx, typename Ta
 // ---------------------------------------------------------------------------
 template <typename R> struct LdsLayout {
     size_t off_cnt, off_frame, off_media, off_zb, off_if, off_lm, off_lay, off_tris, off_nodes, off_links, off_hist, off_march, off_math, total;
+    // Slab walks keep origin / inverse voxel size in registers (LT_INV_MODE 1), so the frame block's last nine values (bytes
+    // 6 R ... 15 R of it) are theirs to use -- at offsets that are constants of the build, so a read is `ds_read ... offset:`
+    // from the zero base the kernel holds for its LDS counters, and no layout moves:
+    //   kSlabDim   the grid's three dimensions as u32 (16-byte aligned; f32: the frame block's last 12 bytes + 4 of its padding)
+    //   kSlabCap   u64: photons that met the step cap (they are counted as stepping where the wave counts its live lanes)
+    static constexpr size_t kCntBytes = 8 * sizeof(double), kFrame = (kCntBytes + 15) & ~(size_t)15;      // the counters lead, the frame block follows
+    static constexpr size_t kSlabDim = kFrame + 48, kSlabCap = kFrame + (sizeof(R) == 8 ? 64 : 32);
     __host__ __device__ LdsLayout(int n_media, int n_layers, int n_tris, int n_nodes, unsigned n_hist = 0, size_t march_bytes = 0)
     {
         auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
         size_t o = 0;
-        off_cnt = o;   o = al(o + 8 * sizeof(double));
+        off_cnt = o;   o = al(o + kCntBytes);      // = kFrame
         off_frame = o; o = al(o + 15 * sizeof(R));     // frame of the source normal (area sources) + the grid's origin / inverse voxel / dimensions
         off_media = o; o = al(o + (size_t)n_media * sizeof(MedD<R>));
         off_zb = o;    o = al(o + (size_t)(n_layers + 1) * sizeof(R));
@@ -284,6 +291,15 @@ constexpr unsigned kMarchDrainMin = LT_MARCH_DRAIN_MIN;
 #endif
 #ifndef LT_INV_MODE_MARCH
 #define LT_INV_MODE_MARCH 2
+#endif
+// the two optional forms of the f64 slab walk's step diet, for same-box A/B builds (profiles/r12a_step_diet_ab.log):
+//   LT_DIET_SIGN32    the in-grid test's sign test on the coordinates' high words alone
+//   LT_DIET_MASKSUM   deposit and energy sums under the in-grid lane mask instead of selects
+#ifndef LT_DIET_SIGN32
+#define LT_DIET_SIGN32 1
+#endif
+#ifndef LT_DIET_MASKSUM
+#define LT_DIET_MASKSUM 1
 #endif
 #define LT_INV_MODE LT_INV_MODE_SLAB
 #define LT_WALK_NAME walk_kernel

@@ -58,6 +58,11 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
     // the register and scratch figures of the mesh kernels built with all of them and with the 32-bit cursor alone.
     constexpr bool kSlabForm = LT_WALK_BATCH == 0;
     constexpr bool kLean = kSlabForm && !CAPTURE;
+    // The step diet of DESIGN.md section 5 (dimensions from LDS, one product for the deposit, masked sums, the scalar step count, the
+    // interface decision as a mask): the f64 slab walks.  The f32 slab walks keep their text: their only yardstick is that every f32
+    // build rounds alike (tests/test_walk_invariances.py), and with these forms the bulk and tail kernels no longer did.
+    constexpr bool kDiet = kSlabForm && sizeof(R) == 8;
+    constexpr bool kMaskSum = kDiet && kLean && LT_DIET_MASKSUM != 0;      // (and LT_DIET_SIGN32: the two optional forms, lt_walk.hip)
 #if LT_WALK_BATCH == 2
     constexpr int PHASE = 0;
 #endif
@@ -89,7 +94,12 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
     const MedD<R>* s_med = reinterpret_cast<const MedD<R>*>(lds_raw + L.off_media);
     const R* s_zb = reinterpret_cast<const R*>(lds_raw + L.off_zb);
     const int32_t* s_lm = reinterpret_cast<const int32_t*>(lds_raw + L.off_lm);
-    [[maybe_unused]] const LayD<R>* s_lay = reinterpret_cast<const LayD<R>*>(lds_raw + L.off_lay);      // slab walks: the per-layer step records
+    // slab walks: the per-layer step records.  kLean builds that read the record at the top of the step hold the table's offset in a
+    // VGPR (one of the two the per-lane step count left): as a scalar it was moved into one in every step -- the record's address is
+    // a 24-bit multiply-add whose other factor is a scalar already -- and in the bulk kernel it was a spilled scalar besides.
+    unsigned lay_off = (unsigned)L.off_lay;
+    if constexpr (kDiet && !CAPTURE && PHASE != 2) asm volatile("" : "+v"(lay_off));
+    [[maybe_unused]] const LayD<R>* s_lay = reinterpret_cast<const LayD<R>*>(lds_raw + lay_off);
     const IfD<R>* s_if = reinterpret_cast<const IfD<R>*>(lds_raw + L.off_if);
     const TriD<R>* s_tris = GEOM == 2 ? reinterpret_cast<const TriD<R>*>(P.tris)
                                       : reinterpret_cast<const TriD<R>*>(lds_raw + L.off_tris);
@@ -107,6 +117,23 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
         onb(nrm, v2, v3);
 #pragma unroll
         for (int k = 0; k < 3; k++) { s_frame[k] = v2[k]; s_frame[3 + k] = v3[k]; }
+    }
+    // Slab walks: the grid's dimensions for the in-grid test, and the count of capped photons (LdsLayout::kSlabDim / kSlabCap).
+    // As kernel arguments the three dimensions were spilled scalars in the log build, restored by four v_readlane in every step.
+    constexpr bool kDimLds = kDiet && LT_INV_MODE != 2;
+    // the photon-step count on the scalar unit (see `steps_w` at the step); the vertex capture keeps its per-lane counter
+    constexpr bool kStepsScalar = kLean && kDimLds;
+    if constexpr (kDimLds) {
+        typedef LdsLayout<R> LL;
+        static_assert(LL::kSlabDim % 16 == 0 && LL::kSlabDim >= LL::kFrame + 6 * sizeof(R) && LL::kSlabDim + 16 <= ((LL::kFrame + 15 * sizeof(R) + 15) & ~(size_t)15),
+                      "the dimensions: behind the source frame, inside the frame block");
+        static_assert(LL::kSlabCap % 8 == 0 && LL::kSlabCap >= LL::kFrame + 6 * sizeof(R) && LL::kSlabCap + 8 <= LL::kFrame + 15 * sizeof(R) &&
+                      (LL::kSlabCap + 8 <= LL::kSlabDim || LL::kSlabCap >= LL::kSlabDim + 16), "the capped count: likewise, clear of the dimensions");
+        if (threadIdx.x == 128 % blockDim.x) {
+            unsigned* d = reinterpret_cast<unsigned*>(lds_raw + LdsLayout<R>::kSlabDim);
+            d[0] = (unsigned)P.nx; d[1] = (unsigned)P.ny; d[2] = (unsigned)P.nz; d[3] = 0u;
+            *reinterpret_cast<unsigned long long*>(lds_raw + LdsLayout<R>::kSlabCap) = 0ull;
+        }
     }
 #if LT_INV_MODE == 2
     const R* s_inv = s_frame + 6;       // grid origin, inverse voxel size, dimensions (see LT_INV_MODE below)
@@ -144,6 +171,13 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
     // per-lane accumulators of the frequent events
     double acc_abs = 0.0, acc_lost = 0.0;
     unsigned long long acc_steps = 0;
+    // kStepsScalar: the photon-steps of the whole wave instead, counted on the scalar unit.  The lanes that take a step in an
+    // iteration are the live ones less those that meet the step cap, and a count inside the step's branch would be a per-lane value
+    // again (the lanes outside the branch keep the old one), so it is taken where the wave is whole: the live lanes at the top of
+    // the step (the bits `need` leaves clear: s_andn2 / s_bcnt1 / s_add / s_addc), less the photons the bulk kernel hands over
+    // behind that (in its wave-uniform block), less the capped ones (counted in LDS where they are capped, taken off once per
+    // workgroup at the end).  All integers: the total is exact.
+    [[maybe_unused]] unsigned long long steps_w = 0;
     // run-length accumulation: consecutive deposits into the same voxel (a third of all steps when the
     // voxel is one mean free path wide) are summed in registers and sent as ONE atomic request
     typedef typename TallyT<TALLY>::type TV;
@@ -363,6 +397,8 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
         // nothing for a wave without a live lane: kept beyond it, `need` costs the bulk kernel a scalar pair it does not have (the
         // log's pointers were spilled instead, and restored in every append).  The kernels that are not kLean ask `alive` again, below.
         if constexpr (kLean) if (need == __ballot(true)) break;
+        // (the empty asm takes the sum here: left alone it sinks to the end of the step, and `need` and a copy of exec live through it)
+        if constexpr (kStepsScalar) { steps_w += (unsigned)__popcll(__ballot(true) & ~need); asm volatile("" : "+s"(steps_w)); }      // the live lanes: each steps, or is capped
         if constexpr (PHASE == 1) {
             // bulk: nothing left to refill with and few lanes alive -> hand them over and leave (see "Tail split" above)
             if (q_done && pk_next >= pk_end && !dumped) {
@@ -396,7 +432,11 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                         }
                     }
                     dumped = true;
-                    if constexpr (kLean) if (!__any(alive)) break;
+                    if constexpr (kStepsScalar) {      // (the lanes handed over take no step here: off the count they were just put on)
+                        const unsigned long long left = __ballot(alive);
+                        steps_w -= na - (unsigned)__popcll(left);
+                        if (left == 0ull) break;
+                    } else if constexpr (kLean) if (!__any(alive)) break;
                 }
             }
         }
@@ -673,9 +713,10 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
         if (alive) {
             if (step >= max_steps) {
                 atomicAdd(&s_cnt[CW_CAPPED], (double)w); alive = false;
+                if constexpr (kStepsScalar) atomicAdd(reinterpret_cast<unsigned long long*>(lds_raw + LdsLayout<R>::kSlabCap), 1ull);
             } else {
                 step++;
-                acc_steps++;
+                if constexpr (!kStepsScalar) acc_steps++;
                 // mesh walks: the clearance of the current cell is a dependent global load; requested here, before the
                 // ~150 instructions of RNG and logarithm, its latency is hidden by the time the hop length is known
                 float clr = -1.0f;   // no grid / outside it: always query
@@ -729,7 +770,14 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                 const R s = (mu_t > 0) ? sleft * inv_mu_t : inf;
 
                 // ---- hop: distance to the next boundary ----
-                R tb = inf; int hit_tri = -1;
+                // Whether the hop ends on an interface is carried as a mask: `near` lanes whose quotient is <= s (a NaN quotient, 0 / 0,
+                // is not), empty where no lane of the wave is near.  tb is read by those lanes alone, so it has no default: an
+                // infinity written in front of the hop and again in the no-lane-near arm was four moves and an all-lane compare per
+                // step.  (The one lane that is not near and yet passed `inf <= inf` -- uz == 0 in a medium without interaction, s == inf:
+                // with uz != 0 an infinite s makes every lane near -- is given its infinity and its bit in the arm of `uz != 0`.)
+                R tb; int hit_tri = -1;
+                bool hop_ends_at_plane = false;
+                if constexpr (kDiet && kLean) asm volatile("" : "=v"(tb)); else tb = inf;
                 if constexpr (!MESH) {
                     if (uz != 0) {
                         const R dz = (uz > 0 ? z_hi : z_lo) - pz;   // the layer's own bounds, from its record: sign of uz, or 0
@@ -741,8 +789,10 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                         if (__any(near)) {   // wave-uniform skip; the empty asm keeps the quotient from being hoisted
                             R den = uz;      // back out and turned into a select
                             asm volatile("" : "+v"(den));
-                            if (near) tb = dz / den;
+                            if (near) { tb = dz / den; if constexpr (kDiet) hop_ends_at_plane = tb <= s; }
                         }
+                    } else if constexpr (kDiet) {
+                        if (s == inf) { tb = inf; hop_ends_at_plane = true; }      // uz == 0 and no interaction: `inf <= inf`, as ever
                     }
                 } else {
                     // clearance grid: every triangle is farther than `c` from every point of this cell, so a hop of
@@ -754,8 +804,11 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                         if (hit_tri >= 0) tb = th;
                     }
                 }
+                const bool at_boundary = kDiet ? hop_ends_at_plane : (tb <= s);
 #endif
+#if LT_WALK_BATCH
                 const bool at_boundary = MESH ? (hit_tri >= 0) : (tb <= s);
+#endif
                 if (!at_boundary && !(s < inf)) {
                     atomicAdd(&s_cnt[MESH ? CW_ESC_MESH : CW_CAPPED], (double)w); alive = false;
                 } else if (at_boundary) {
@@ -834,7 +887,16 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                     // (slab kernels; the mesh kernels' scalar file has no room for the three dimensions: they compare in walk
                     //  precision against the copies they keep in LDS)
                     bool inside;
-                    if constexpr (!MESH) inside = (int)(Mx<R>::sign_word(fx) | Mx<R>::sign_word(fy) | Mx<R>::sign_word(fz)) >= 0 &&
+                    if constexpr (kDimLds) {
+                        // the three dimensions by one 16-byte LDS read at a constant address (kSlabDim): no VALU instruction and no
+                        // scalar register held over the loop
+                        const uint4 gd = *reinterpret_cast<const uint4*>(lds_raw + LdsLayout<R>::kSlabDim);
+                        // (the sign words pass through an empty asm: left visible, the compiler widens the f64 test to both words of
+                        //  each coordinate -- two v_or3_b32 and a 64-bit compare for one v_or3_b32 and a 32-bit one)
+                        unsigned sg = Mx<R>::sign_word(fx) | Mx<R>::sign_word(fy) | Mx<R>::sign_word(fz);
+                        if constexpr (LT_DIET_SIGN32 != 0) asm("" : "+v"(sg));
+                        inside = (int)sg >= 0 && vx < gd.x && vy < gd.y && vz < gd.z;
+                    } else if constexpr (!MESH) inside = (int)(Mx<R>::sign_word(fx) | Mx<R>::sign_word(fy) | Mx<R>::sign_word(fz)) >= 0 &&
                                                   vx < (unsigned)P.nx && vy < (unsigned)P.ny && vz < (unsigned)P.nz;
                     else inside = fx >= 0 && fx < fnx && fy >= 0 && fy < fny && fz >= 0 && fz < fnz;
                     // the tile of the voxel (log mode).  <= 65536 tiles, so on a lane inside the grid every factor and sum is below
@@ -857,10 +919,34 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                     const bool same = inside && idx == pend_idx;
                     const bool flush = inside && !same;
                     f_idx = flush ? pend_idx : kNoVoxel; f_val = pend_val;
+                    if constexpr (kDiet) {
+                        // One sum for both cases: onto the run (same voxel) or onto zero (a new run), kept where the lane is inside.
+                        // Where the tally has the walk's type the product was contracted into the sum, pend_val + w dep in one FMA,
+                        // and the new run's value was a second product; now the one FMA serves both: fma(w, dep, +0) rounds as
+                        // w dep does, and w > 0, dep >= 0, so no -0 arises.  The other tallies add the quantum: 0 + q is q.
+                        // The plain walks: the lanes inside take the sum, the new index and the absorbed weight under their mask and
+                        // the others the lost weight under its complement -- x + 0.0 is x, and the sums start at +0.0 -- instead of
+                        // eight selects between them.
+                        if constexpr (kMaskSum) {
+                            if (inside) {
+                                const TV base = same ? pend_val : (TV)0;
+                                if constexpr (std::is_same<TV, R>::value) pend_val = Mx<R>::fma(w, LT_STEP_DEP, base); else pend_val = base + q;
+                                pend_idx = idx;      // (same: the index it holds)
+                                acc_abs += (double)dw;
+                            } else acc_lost += (double)dw;
+                        } else {
+                            const TV base = flush ? (TV)0 : pend_val;
+                            TV t;
+                            if constexpr (std::is_same<TV, R>::value) t = Mx<R>::fma(w, LT_STEP_DEP, base); else t = base + q;
+                            pend_val = inside ? t : pend_val;
+                        }
+                    } else
                     pend_val = same ? pend_val + q : (flush ? q : pend_val);
-                    pend_idx = flush ? idx : pend_idx;
-                    acc_abs += inside ? (double)dw : 0.0;
-                    acc_lost += inside ? 0.0 : (double)dw;
+                    if constexpr (!kMaskSum) {
+                        pend_idx = flush ? idx : pend_idx;
+                        acc_abs += inside ? (double)dw : 0.0;
+                        acc_lost += inside ? 0.0 : (double)dw;
+                    }
                     w = sub_rounded(w, dw);
                     if (!(w > 0)) alive = false;
                     else {
@@ -921,7 +1007,8 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
 #endif
     // ---------------- flush counters ----------------
     const double wa = wave_sum(acc_abs), wl = wave_sum(acc_lost);
-    const unsigned long long ws = wave_sum(acc_steps);
+    unsigned long long ws;
+    if constexpr (kStepsScalar) ws = steps_w; else ws = wave_sum(acc_steps);
     if (lane == 0) {
         atomicAdd(&s_cnt[CW_ABSORBED], wa);
         atomicAdd(&s_cnt[CW_LOST], wl);
@@ -932,6 +1019,10 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
         for (unsigned t = threadIdx.x; t < P.log_n_hist; t += blockDim.x)
             if (s_hist[t]) __hip_atomic_fetch_add(&P.log_hist[t * kLogGroups + (blockIdx.x & (kLogGroups - 1))], s_hist[t],
                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (kStepsScalar) if (threadIdx.x == 16 % blockDim.x) {      // the capped photons took no step: off the waves' counts (mod 2^64)
+        const unsigned long long capped = *reinterpret_cast<const unsigned long long*>(lds_raw + LdsLayout<R>::kSlabCap);
+        if (capped) __hip_atomic_fetch_add(&P.counters->steps, 0ull - capped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (PHASE != 2 && blockIdx.x == 0 && threadIdx.x == 8)      // (the tail's photons were counted by the bulk kernel)
         __hip_atomic_fetch_add(&P.counters->photons, P.n_photons, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (threadIdx.x < 8)
