@@ -1002,20 +1002,19 @@ template <typename R, bool LEAN = false> LT_DEV void disk(R u0, R u1, R* d)
 }
 
 // cosine_weighted_hemisphere_sampling, S/utils.py:132-161
-// (cosine_hemi_frame: the same with the frame of n handed in -- the walk's source normal is the same for every photon, its
-// frame is made once per workgroup and kept in LDS instead of being carried through the hot loop in registers)
-template <typename R> LT_DEV void cosine_hemi_frame(const R* n, const R* v2, const R* v3, const R* wi_in, R u0, R u1, R* out)
+// (cosine_lobe_frame: the walk's EMISSION, role of cosine_weighted_light_sampling, S/light_samples.py:64-85 -- a cosine lobe
+// about the source normal n, whatever way n points.  It has no incoming direction: utils.py:145-146 mirrors the lobe when
+// the z of a direction in the SURFACE's frame is negative, and applied to a source normal in world coordinates that test sent
+// the photons of every source with n.z < 0 into the hemisphere behind it.  Same disk map and frame as cosine_hemi; the frame
+// of n is handed in -- the source normal is the same for every photon, its frame is made once per workgroup and kept in LDS.)
+template <typename R> LT_DEV void cosine_lobe_frame(const R* n, const R* v2, const R* v3, R u0, R u1, R* out)
 {
-    R wiz = -wi_in[2];  // :133
     R d[2]; disk(u0, u1, d);
     R zz = (R)1 - d[0] * d[0] - d[1] * d[1];
     R z = Mx<R>::sqrt(zz > 0 ? zz : (R)0);  // :138
-    R oz = z;
-    if (wiz < 0) oz = -oz;  // :145-146
-    R pdf = (wiz * oz > 0) ? Mx<R>::abs(z) * (R)0.3183098861837907 : (R)0;  // :149-152
 #pragma unroll
-    for (int k = 0; k < 3; k++) out[k] = d[0] * v2[k] + d[1] * v3[k] + oz * n[k];  // :154-157
-    out[3] = pdf;
+    for (int k = 0; k < 3; k++) out[k] = d[0] * v2[k] + d[1] * v3[k] + z * n[k];  // :154-157
+    out[3] = z * (R)0.3183098861837907;
 }
 template <typename R, bool LEAN = false> LT_DEV void cosine_hemi(const R* n, const R* wi_in, R u0, R u1, R* out)
 {

@@ -337,11 +337,10 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
                     }
                     grp++;
                     R nrm[3] = {(R)P.src_dir[0], (R)P.src_dir[1], (R)P.src_dir[2]};
-                    R wi[3] = {-nrm[0], -nrm[1], -nrm[2]};
                     R o4[4];
                     {
                         const R v2[3] = {s_frame[0], s_frame[1], s_frame[2]}, v3[3] = {s_frame[3], s_frame[4], s_frame[5]};
-                        cosine_hemi_frame(nrm, v2, v3, wi, u4[2], u4[3], o4);
+                        cosine_lobe_frame(nrm, v2, v3, u4[2], u4[3], o4);
                     }
                     e_pdf_dir = Mx<R>::abs(o4[0] * nrm[0] + o4[1] * nrm[1] + o4[2] * nrm[2]) * (R)0.3183098861837907;   // |cos| / pi, S/light_samples.py:83
                     ux = o4[0]; uy = o4[1]; uz = o4[2];

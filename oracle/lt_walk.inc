@@ -211,6 +211,20 @@ static inline void SFX(cosine_hemi)(const R* n, const R* wi_in, R u0, R u1, R* o
     out[3] = pdf;
 }
 
+/* The walk's emission, role of cosine_weighted_light_sampling (S/light_samples.py:64-85): a cosine lobe about the source
+ * normal n, whatever way n points -- an emitter has no incoming direction, and cosine_hemi's mirror test (:145-146, meant for
+ * the z of a direction in the surface's own frame) sent the photons of a source with n.z < 0 into the hemisphere behind it.
+ * Same disk map and frame as cosine_hemi. */
+static inline void SFX(cosine_lobe)(const R* n, R u0, R u1, R* out)
+{
+    R d[2]; SFX(disk)(u0, u1, d);
+    R zz = (R)1 - d[0] * d[0] - d[1] * d[1];
+    R z = RSQRT(zz > 0 ? zz : 0);
+    R v2[3], v3[3]; SFX(onb)(n, v2, v3);
+    for (int k = 0; k < 3; k++) out[k] = d[0] * v2[k] + d[1] * v3[k] + z * n[k];
+    out[3] = z * (R)0.3183098861837907;
+}
+
 /* get_reflected_direction, S/brdf.py:8-9 */
 static inline void SFX(reflect)(const R* v, const R* n, R* o)
 {
@@ -372,8 +386,7 @@ static void SFX(walk_one)(const SFX(world)* W, SFX(acc)* A, uint64_t pid)
     if (sc->src_type == LT_SRC_COSINE_QUAD) {
         SFX(uniforms)(W, &rng, pid, grp++, u4);
         R o4[4];
-        R wi[3] = {-W->src_dir[0], -W->src_dir[1], -W->src_dir[2]};
-        SFX(cosine_hemi)(W->src_dir, wi, u4[2], u4[3], o4);
+        SFX(cosine_lobe)(W->src_dir, u4[2], u4[3], o4);
         e_pdf_dir = RFABS(o4[0] * W->src_dir[0] + o4[1] * W->src_dir[1] + o4[2] * W->src_dir[2]) * (R)0.3183098861837907; /* |cos| / pi, S/light_samples.py:83 */
         { R cr[3]; SFX(cross3)(W->src_e1, W->src_e2, cr); e_pdf_pos = (R)1 / RSQRT(SFX(dot3)(cr, cr)); }
         for (int k = 0; k < 3; k++) {
