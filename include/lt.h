@@ -74,7 +74,12 @@ extern "C" {
 typedef struct lt_medium {
     double mu_a; /* absorption coefficient  [1/length] */
     double mu_s; /* scattering coefficient  [1/length] */
-    double g;    /* Henyey-Greenstein anisotropy (medium_samples.py:14-16) */
+    double g;    /* Henyey-Greenstein anisotropy (medium_samples.py:14-16), any
+                    |g| < 1: sampled without cancellation down to g = 0; a g
+                    that rounds to +-1 in an f32 walk is taken as the largest
+                    float below 1.  The deflection cosine is good to a few
+                    roundings of the walk's precision for |g| <= 0.9 and loses
+                    a factor ~ 1 / (1 - |g|)^2 of it towards |g| = 1 */
     double n;    /* refractive index */
 } lt_medium;
 
@@ -533,6 +538,7 @@ int lt_intersect_bounds(lt_ctx* ctx, const double* origins, const double* dirs,
 #define LT_FN_WALK_MATH 8 /* in: x in (0,1]  out: [5] -ln x, sin 2 pi x, cos 2 pi x, sqrt x, 1/(1+x) -- the walk's f64 primitives */
 #define LT_FN_WALK_MATH_RAW 9 /* in: k = a raw 32-bit draw (as a double)  out: [3] -ln u, sin 2 pi u, cos 2 pi u of u = (k + 1) 2^-32, by the forms the f64 XORWOW walk uses on the raw draw */
 #define LT_FN_PLANE_REACH 10 /* in: o[3], d[3], tri[3][3], s, f32 (0 / 1)  out: [2] reach, t -- the mesh walk's plane pre-test (1: a hop of length s from o along d may reach the triangle's plane; 0: rejected without a triangle test) and the triangle test's own t (NaN: none), both in walk precision (f32 != 0: float) on the triangle record a launch uploads.  o, d, s are narrowed to float as given: pass values a float holds.  The pre-test is sound when no row has reach = 0 with 1e-6 < t < s */
+#define LT_FN_HG_WALK 11 /* in: xi, f32 (0 / 1), then the 12 values of one medium record exactly as lt_layer_records returned them for that precision  out: [2] the deflection cosine as the walk takes it (clamped to [-1, 1]), in walk precision (f32 != 0: float; pass an xi a float holds), from the medium table (mesh walks) and from the layer record (slab walks) */
 int lt_eval(lt_ctx* ctx, int fn, const double* in, size_t n, double* out);
 /* first `count` raw 32-bit XORWOW outputs of photon `photon_id` under `seed`
  * (checks the per-photon seeding against the oracle's restatement) */

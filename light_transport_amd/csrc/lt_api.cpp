@@ -251,11 +251,18 @@ void fill_media(const std::vector<lt_medium>& in, int quantity, std::vector<MedD
         m.inv_mu_t = (R)(mu_t > 0 ? 1.0 / mu_t : 0.0);
         m.absorb = (R)(mu_t > 0 ? in[i].mu_a / mu_t : 0.0);
         m.g = (R)in[i].g;
+        // a g that lt_set_media accepted (|g| < 1 in double) may round to +-1 in float.  At g = -1.0f the sampling's
+        // denominator (1 - g) + 2 g xi = 2 - 2 xi is 0 at xi = 1.0f, which rocrand_uniform returns, and 0 / 0 is NaN (at
+        // g = +1.0f nothing divides by zero: 1 - g^2 = 0 and every cosine is 1).  Such a g is narrowed towards zero instead, to
+        // the largest float below 1
+        if (std::fabs(in[i].g) < 1.0 && !(std::fabs((double)m.g) < 1.0))
+            m.g = std::nextafter(m.g, (R)0);
         m.n = (R)in[i].n;
         const R g = m.g;  // derived in walk precision, one operation each
         m.one_m_g2 = (R)1 - g * g;
         m.one_p_g2 = (R)1 + g * g;
-        m.inv_2g = g != 0 ? (R)1 / ((R)2 * g) : (R)0;
+        // 0 marks the media that hg_sample_walk samples by hg_small_g: g = 0 as ever, and every |g| < kHgSmallG
+        m.inv_2g = std::fabs((double)g) >= kHgSmallG ? (R)1 / ((R)2 * g) : (R)0;
         m.dep = quantity == LT_QUANTITY_FLUENCE ? m.inv_mu_t : m.absorb;
         m.one_m_g = (R)1 - g; m.two_g = (R)2 * g;
         m.pad_ = 0;
@@ -2346,8 +2353,8 @@ int lt_intersect_bounds(lt_ctx* c, const double* origins, const double* dirs, co
 int lt_eval(lt_ctx* c, int fn, const double* in, size_t n, double* out)
 {
     CHECK_CTX(c);
-    static const int k_in[11] = {2, 2, 3, 2, 8, 6, 8, 5, 1, 1, 21}, k_out[11] = {1, 1, 6, 2, 4, 3, 5, 3, 5, 3, 2};
-    if (fn < 0 || fn > 10) return c->fail(LT_E_INVALID, "lt_eval: unknown function %d", fn);
+    static const int k_in[12] = {2, 2, 3, 2, 8, 6, 8, 5, 1, 1, 21, 14}, k_out[12] = {1, 1, 6, 2, 4, 3, 5, 3, 5, 3, 2, 2};
+    if (fn < 0 || fn > 11) return c->fail(LT_E_INVALID, "lt_eval: unknown function %d", fn);
     if (n == 0) return LT_OK;
     if (!in || !out) return c->fail(LT_E_INVALID, "lt_eval: null argument");
     BIND(c);

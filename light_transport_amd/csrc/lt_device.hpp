@@ -327,6 +327,7 @@ template <> struct Mx<double> {
     static LT_DEV double abs(double x) { return ::fabs(x); }
     static LT_DEV double fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
     static LT_DEV double clamp_unit(double c) { return __builtin_fmax(__builtin_fmin(c, 1.0), -1.0); }
+    static LT_DEV double clamp_unit_lo_first(double c) { return __builtin_fmin(__builtin_fmax(c, -1.0), 1.0); }   // the same value
     static LT_DEV double sin(double x) { return ::sin(x); }
     static LT_DEV double cos(double x) { return ::cos(x); }
     // the hot-loop forms (restricted ranges, see above)
@@ -357,6 +358,7 @@ template <> struct Mx<float> {
     static LT_DEV float abs(float x) { return ::fabsf(x); }
     static LT_DEV float fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
     static LT_DEV float clamp_unit(float c) { return __builtin_fmaxf(__builtin_fminf(c, 1.0f), -1.0f); }
+    static LT_DEV float clamp_unit_lo_first(float c) { return __builtin_fminf(__builtin_fmaxf(c, -1.0f), 1.0f); }
     static LT_DEV float sin(float x) { return ::sinf(x); }
     static LT_DEV float cos(float x) { return ::cosf(x); }
     static LT_DEV float neg_log(float xi, const double*) { return -::logf(xi); }
@@ -954,20 +956,44 @@ template <typename R> LT_DEV R hg_sample(R xi, R g, R one_m_g2, R one_p_g2, R in
     return Mx<R>::clamp_unit(c);   // [-1, 1]
 }
 
-// ... as the walk takes it: the denominator from the medium record ((1 - g) + (2 g) xi, one fused product) and NO clamp -- the
-// value leaves [-1, 1] by a rounding at most, which sqrt01 (sin theta) absorbs and the direction update does not notice.
+// The same law for |g| < kHgSmallG (lt_internal.hpp; g = 0 included), where the form above cancels: ((1 + g^2) - t^2) / (2 g)
+// loses a factor 1 / (2 |g|) of its precision, every bit of it from |g| ~ 1e-8 (f32) and 1e-16 (f64) on.  With s = 2 xi - 1
+//     cos = s + g (1 - s^2) (3 + 2 g s - g^2) / (2 (1 + g s)^2),
+// the identical function of (xi, g) written as the isotropic answer plus a correction of order g: nothing cancels, and at
+// g = 0 it is 2 xi - 1 to the bit.  |cos| <= 1 but for roundings: at s = +-1 the correction is an exact 0.
+// (The multiply-adds are written out: left to the compiler, the f32 builds fused different ones in different kernels -- where it
+// packed two of the products into one v_pk_mul_f32 the sum behind them stayed unfused -- and the medium-table and layer-record
+// walks, and the oracle, which takes the same sequence, differed in the last bit.)
+template <typename R> LT_DEV R hg_small_g(R xi, R g)
+{
+    const R s = Mx<R>::fma((R)2, xi, (R)-1);
+    const R d = Mx<R>::fma(g, s, (R)1);
+    const R a = Mx<R>::fma(-s, s, (R)1);
+    const R b = Mx<R>::fma(g, Mx<R>::fma((R)2, s, -g), (R)3);
+    // (a rounding of 1 at most; see hg_sample_walk.  Lower bound first, the reverse of clamp_unit: two clamps of one shape
+    // the compiler merges behind the walk's branch, where the quotient path then pays a third instruction to canonicalise)
+    return Mx<R>::clamp_unit_lo_first(s + Mx<R>::quot((g * a) * b, (R)2 * (d * d)));
+}
+
+// ... as the walk takes it: the denominator from the medium record ((1 - g) + (2 g) xi, one fused product).  The host gives
+// every |g| < kHgSmallG the record inv_2g = 0, which selects hg_small_g (within a rounding of [-1, 1]).  The quotient form is
+// clamped, as hg_sample and the oracle clamp it: its value leaves [-1, 1] by MORE than a rounding where the denominator
+// cancels -- 19 ulp at g = -0.9 in f64, 4e-4 at g = -0.999 in f32 -- and spin_turn scales the direction by it
+// (LT_FN_HG_WALK: |cos| <= 1 + 4 ulp over the whole range of g, tests/test_gpu_hg_walk.py).  What it returns is in [-1, 1]
+// exactly, so 1 - cos^2 >= 0 and the walk's spin needs no guard of its own (spin_turn<R, true>): the clamp costs the quotient
+// path two instructions and saves it one.
 template <typename R> LT_DEV R hg_sample_walk(R xi, const MedD<R>* M)
 {
-    if (M->g == 0) return (R)2 * xi - (R)1;
+    if (M->inv_2g == 0) return hg_small_g(xi, M->g);
     const R t = Mx<R>::quot(M->one_m_g2, M->two_g * xi + M->one_m_g);
-    return (M->one_p_g2 - t * t) * M->inv_2g;
+    return Mx<R>::clamp_unit((M->one_p_g2 - t * t) * M->inv_2g);
 }
-// ... and from the slab walk's layer record (LayD: the same bits; two_g = 2 g is 0 exactly when g is)
+// ... and from the slab walk's layer record (LayD: the same bits; inv_2g is 0 exactly for |g| < kHgSmallG, and g = two_g / 2)
 template <typename R> LT_DEV R hg_sample_walk(R xi, R two_g, R one_m_g, R one_m_g2, R one_p_g2, R inv_2g)
 {
-    if (two_g == 0) return (R)2 * xi - (R)1;
+    if (inv_2g == 0) return hg_small_g(xi, (R)0.5 * two_g);
     const R t = Mx<R>::quot(one_m_g2, two_g * xi + one_m_g);
-    return (one_p_g2 - t * t) * inv_2g;
+    return Mx<R>::clamp_unit((one_p_g2 - t * t) * inv_2g);
 }
 
 // create_orthonormal_system, S/utils.py:72-80
@@ -1101,9 +1127,10 @@ template <typename R> LT_DEV R boundary_planar(R uz, R n1, R n2, R Nr, R* cos_t_
 }
 
 // Spin (App. C.6): MCML direction update, |uz| > 0.99999 special case.
-template <typename R> LT_DEV void spin_turn(R* u, R ct, R sp, R cp)      // sp, cp: sin / cos of the azimuth
+// (UNIT: the caller guarantees |ct| <= 1, as hg_sample_walk does; then 1 - ct^2 needs no guard, and it has the same bits)
+template <typename R, bool UNIT = false> LT_DEV void spin_turn(R* u, R ct, R sp, R cp)      // sp, cp: sin / cos of the azimuth
 {
-    const R st2 = Mx<R>::max0((R)1 - ct * ct);          // sin^2(theta); a rounding-negative value is 0
+    const R st2 = UNIT ? (R)1 - ct * ct : Mx<R>::max0((R)1 - ct * ct);          // sin^2(theta); a rounding-negative value is 0
     R ux = u[0], uy = u[1], uz = u[2];
     if (Mx<R>::abs(uz) > (R)0.99999) {
         const R st = Mx<R>::sqrt_unit(st2);
@@ -1122,10 +1149,10 @@ template <typename R> LT_DEV void spin_turn(R* u, R ct, R sp, R cp)      // sp, 
         u[2] = uz * ct - sc * t2;
     }
 }
-template <typename R, bool TABLE> LT_DEV void spin(R* u, R ct, typename HeldU<R, TABLE>::type xi_phi, const double* T)      // xi_phi: the azimuth's uniform as the walk carries it (f64 XORWOW: the raw draw); T: kWalkMathTab or its LDS copy
+template <typename R, bool TABLE, bool UNIT = false> LT_DEV void spin(R* u, R ct, typename HeldU<R, TABLE>::type xi_phi, const double* T)      // xi_phi: the azimuth's uniform as the walk carries it (f64 XORWOW: the raw draw); T: kWalkMathTab or its LDS copy
 {
     R sp, cp; HeldU<R, TABLE>::sincos_turn(xi_phi, T, &sp, &cp);
-    spin_turn(u, ct, sp, cp);
+    spin_turn<R, UNIT>(u, ct, sp, cp);
 }
 
 // ---------------------------------------------------------------------------

@@ -9,12 +9,17 @@
 
 namespace ltk {
 
+// |g| below which the walk samples Henyey-Greenstein by hg_small_g (lt_device.hpp) instead of the quotient form, whose error
+// grows as eps / (2 |g|): at 2^-6 the quotient form is 7.5e-6 (f32) / 1.1e-14 (f64) off, ten times its error at g = 0.3 .. 0.9,
+// hg_small_g 6e-8 / 6e-17.  The host marks such a medium by inv_2g = 0, as it always has g = 0.
+constexpr double kHgSmallG = 0.015625;
+
 // Per-medium constants in walk precision R.  Derived values are computed on the
 // host in double, one IEEE operation each, then narrowed.
 template <typename R>
 struct MedD {
     R mu_t, inv_mu_t, absorb, g;
-    R n, one_m_g2, one_p_g2, inv_2g;
+    R n, one_m_g2, one_p_g2, inv_2g;   // inv_2g = 0 for |g| < kHgSmallG: the walk's test for hg_small_g
     R dep;   // what a voxel receives per unit of photon weight at an interaction: absorb, or inv_mu_t (LT_QUANTITY_FLUENCE)
     R one_m_g, two_g;   // the walk's Henyey-Greenstein denominator: (1 - g) + (2 g) xi as one fused product
     R pad_;
@@ -40,9 +45,9 @@ struct alignas(16) LayD {
     R mu_t, inv_mu_t;        // free path
     R z_lo, z_hi;            // the layer's bounds: the step takes z_hi when uz > 0, z_lo otherwise
     R absorb, dep;           // drop
-    R two_g, one_m_g;        // Henyey-Greenstein: denominator (two_g == 0: isotropic) ...
+    R two_g, one_m_g;        // Henyey-Greenstein: denominator ...
     R one_m_g2, one_p_g2;    // ... numerator and offset ...
-    R inv_2g, n;             // ... and scale; the refractive index (the interface table carries it for the slab's own events)
+    R inv_2g, n;             // ... and scale (0: |g| < kHgSmallG, sampled from g = two_g / 2 alone); the refractive index (the interface table carries it for the slab's own events)
 };
 static_assert(sizeof(LayD<double>) == 96 && sizeof(LayD<float>) == 48, "LayD: a whole number of 16-byte quads");
 // (host only, no device needed) the record of every layer from the media / bounds tables the kernels already get

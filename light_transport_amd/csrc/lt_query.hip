@@ -78,6 +78,18 @@ template <typename R> LT_DEV void plane_reach_pair(const double* r, double* out)
     out[1] = (double)tri_hit<R>(o, d, &T);
 }
 
+// one LT_FN_HG_WALK row: every value of it is representable in R (lt_layer_records made the record; the caller rounds xi)
+template <typename R> LT_DEV void hg_walk_pair(const double* r, double* out)
+{
+    MedD<R> M;
+    M.mu_t = (R)r[2]; M.inv_mu_t = (R)r[3]; M.absorb = (R)r[4]; M.g = (R)r[5];
+    M.n = (R)r[6]; M.one_m_g2 = (R)r[7]; M.one_p_g2 = (R)r[8]; M.inv_2g = (R)r[9];
+    M.dep = (R)r[10]; M.one_m_g = (R)r[11]; M.two_g = (R)r[12]; M.pad_ = 0;
+    const R xi = (R)r[0];
+    out[0] = (double)hg_sample_walk<R>(xi, &M);
+    out[1] = (double)hg_sample_walk<R>(xi, M.two_g, M.one_m_g, M.one_m_g2, M.one_p_g2, M.inv_2g);
+}
+
 __global__ void k_eval(int fn, const double* in, size_t n, double* out)
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -125,6 +137,10 @@ __global__ void k_eval(int fn, const double* in, size_t n, double* out)
         const unsigned k = (unsigned)in[i];
         out[3 * i] = neg_log_raw(k, kWalkMathTab);
         sincos_turn_raw(k, kWalkMathTab, &out[3 * i + 1], &out[3 * i + 2]);
+    } break;
+    case LT_FN_HG_WALK: {   // the walk's own deflection cosine, from the medium table and from the layer record, in walk precision
+        const double* r = in + 14 * i;      // xi, f32, then a MedD record as the host built it for that precision
+        if (r[1] != 0.0) hg_walk_pair<float>(r, out + 2 * i); else hg_walk_pair<double>(r, out + 2 * i);
     } break;
     case LT_FN_PLANE_REACH: {   // the walk's plane pre-test beside the triangle test it stands in front of, in walk precision
         const double* r = in + 21 * i;      // o[3], d[3], then the TriD fields a, ab, ac, n as the host filled them, s, f32, this triangle's reach_slack

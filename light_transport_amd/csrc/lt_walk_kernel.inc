@@ -953,10 +953,10 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 8 ? (GEOM == 0 ? LT_F64_SLA
 #if LT_WALK_BATCH == 0
                         if constexpr (kTabEarly) {
                             R sp, cp; sincos_turn_raw(x2, Tsc, &sp, &cp);
-                            spin_turn(u, LT_STEP_HG(u1), sp, cp);
+                            spin_turn<R, true>(u, LT_STEP_HG(u1), sp, cp);       // (hg_sample_walk returns |cos| <= 1)
                         } else
 #endif
-                        spin<R, TABLE>(u, LT_STEP_HG(u1), x2, s_math);
+                        spin<R, TABLE, true>(u, LT_STEP_HG(u1), x2, s_math);
                         ux = u[0]; uy = u[1]; uz = u[2];
                         if (w < (R)1e-4) {  // weight roulette; shape of S/path_tracing_fix1.py:126-132
                             if (HeldU<R, TABLE>::get(x3) <= (R)0.1) { atomicAdd(&s_cnt[CW_ROULETTE], -9.0 * (double)w); w *= (R)10; }

@@ -118,6 +118,12 @@ int lto_triangle_fields(const double* tris, size_t n, double* out)
     return 0;
 }
 
+/* Test hook: while set, every scattering of the walks deflects by exactly 90 degrees (cos = 0) -- what the quotient form of
+ * the Henyey-Greenstein sampling gave in float for every |g| <= 1e-8 before the walk took hg_sample_walk.  A test plants it to
+ * show that its bound would have noticed (tests/test_hg_walk_cpu.py).  Not thread safe against running walks; off by default. */
+static int g_plant_cos0 = 0;
+void lto_plant_cos0(int on) { g_plant_cos0 = on; }
+
 /* ---- instantiate the precision-generic body ------------------------------ */
 #define R double
 #define SFX(n) n##_f64
@@ -126,6 +132,7 @@ int lto_triangle_fields(const double* tris, size_t n, double* out)
 #define RCOS cos
 #define RSQRT sqrt
 #define RFABS fabs
+#define RFMA fma
 #define RNEXT nextafter
 #include "lt_walk.inc"
 #undef R
@@ -135,6 +142,7 @@ int lto_triangle_fields(const double* tris, size_t n, double* out)
 #undef RCOS
 #undef RSQRT
 #undef RFABS
+#undef RFMA
 #undef RNEXT
 
 #define R float
@@ -144,6 +152,7 @@ int lto_triangle_fields(const double* tris, size_t n, double* out)
 #define RCOS cosf
 #define RSQRT sqrtf
 #define RFABS fabsf
+#define RFMA fmaf
 #define RNEXT nextafterf
 #include "lt_walk.inc"
 #undef R
@@ -198,6 +207,11 @@ int lto_eval(int fn, const double* in, size_t n, double* out)
             double u[3] = {in[5 * i], in[5 * i + 1], in[5 * i + 2]};
             spin_f64(u, in[5 * i + 3], in[5 * i + 4]);
             out[3 * i] = u[0]; out[3 * i + 1] = u[1]; out[3 * i + 2] = u[2];
+        } break;
+        case LT_FN_HG_WALK: {   /* a row of the library's query: xi, f32, a 12-value medium record; the oracle takes its g (field 3) */
+            const double* r = in + 14 * i;
+            const double c = r[1] != 0.0 ? (double)hg_sample_walk_f32((float)r[0], (float)r[5]) : hg_sample_walk_f64(r[0], r[5]);
+            out[2 * i] = out[2 * i + 1] = c;
         } break;
         default: return LT_E_INVALID;
         }

@@ -78,6 +78,8 @@ int lto_intersect_rays(const lto_scene* sc, const double* origins, const double*
                        const double* tmax, size_t n, int use_bvh, int32_t* prim_out,
                        double* t_out);
 int lto_rng_raw(uint64_t seed, uint64_t photon_id, uint32_t count, uint32_t* out);
+/* test hook (lt_oracle.c): on != 0 makes every scattering of the walks a 90-degree one until switched off again */
+void lto_plant_cos0(int on);
 /* PreComputedTriangle derived fields (primitives.py:99-112):
  * out[n][16] = centroid[3], edge_1[3], edge_2[3], normal[3], num, pad[3] */
 int lto_triangle_fields(const double* tris, size_t n, double* out);

@@ -2,7 +2,7 @@
  * lt_walk.inc -- precision-generic body of the CPU oracle (TEST INFRASTRUCTURE
  * ONLY, see lt_oracle.h).  Included twice by lt_oracle.c with
  *   R      real type            SFX(name)  name suffixed _f64 / _f32
- *   RLOG RSIN RCOS RSQRT RFABS  libm functions of that precision
+ *   RLOG RSIN RCOS RSQRT RFABS RFMA  libm functions of that precision
  * Reference citations use S/ = LightTransportSimulator/light_transport/src/.
  */
 
@@ -166,6 +166,32 @@ static inline R SFX(hg_sample)(R xi, R g)
         R t = ((R)1 - g * g) / ((R)1 - g + (R)2 * g * xi);
         c = ((R)1 + g * g - t * t) * ((R)1 / ((R)2 * g));
     }
+    if (c > 1) c = 1;
+    if (c < -1) c = -1;
+    return c;
+}
+
+/* ... as the WALK samples it.  The quotient form above cancels as g -> 0: ((1 + g^2) - t^2) / (2 g) is wrong by eps / (2 |g|),
+ * by 1e-10 at g = 1e-6 in double, and in float every scattering is at exactly 90 degrees from |g| = 1e-8 down.  Below
+ * R_HG_SMALL_G (the library's kHgSmallG) the walk takes the same law written as the isotropic answer plus a correction of
+ * order g, in which nothing cancels; at g = 0 it is 2 xi - 1 to the bit. */
+#define R_HG_SMALL_G ((R)0.015625)
+/* the medium's g in walk precision: a |g| < 1 that rounds to 1 in float (1 - g = 0) goes to the largest float below 1 */
+static inline R SFX(narrow_g)(double g)
+{
+    R r = (R)g;
+    if (fabs(g) < 1.0 && !(fabs((double)r) < 1.0)) r = RNEXT(r, (R)0);
+    return r;
+}
+static inline R SFX(hg_sample_walk)(R xi, R g)
+{
+    if (!(RFABS(g) < R_HG_SMALL_G)) return SFX(hg_sample)(xi, g);
+    /* (the fused multiply-adds of the library's hg_small_g, written out there as here) */
+    const R s = RFMA((R)2, xi, (R)-1);
+    const R d = RFMA(g, s, (R)1);
+    const R a = RFMA(-s, s, (R)1);
+    const R b = RFMA(g, RFMA((R)2, s, -g), (R)3);
+    R c = s + ((g * a) * b) / ((R)2 * (d * d));
     if (c > 1) c = 1;
     if (c < -1) c = -1;
     return c;
@@ -516,7 +542,7 @@ static void SFX(walk_one)(const SFX(world)* W, SFX(acc)* A, uint64_t pid)
         p[0] += u[0] * s; p[1] += u[1] * s; p[2] += u[2] * s;
         sleft = 0;
         R dw = w * M->absorb;
-        const R ct_s = SFX(hg_sample)(u4[1], M->g);
+        const R ct_s = g_plant_cos0 ? (R)0 : SFX(hg_sample_walk)(u4[1], M->g);
         SFX(record)(W, rel, &nv, p, u, w, LT_VERTEX_VOLUME, cur, (unsigned)(step + 1), NULL, (R)0,
                     (w - dw > 0) ? SFX(hg_pdf)(-ct_s, M->g) : (R)0);
         SFX(deposit)(W, A, p, dw, w * M->dep);
@@ -553,7 +579,7 @@ static int SFX(prepare)(SFX(world)* W, const lto_scene* sc)
         W->med[i].inv_mu_t = (R)(mu_t > 0 ? 1.0 / mu_t : 0.0);
         W->med[i].absorb = (R)(mu_t > 0 ? sc->media[i].mu_a / mu_t : 0.0);
         W->med[i].dep = sc->quantity == LT_QUANTITY_FLUENCE ? W->med[i].inv_mu_t : W->med[i].absorb;
-        W->med[i].g = (R)sc->media[i].g;
+        W->med[i].g = SFX(narrow_g)(sc->media[i].g);
         W->med[i].n = (R)sc->media[i].n;
     }
     if (sc->n_layers > 0) {
@@ -648,6 +674,7 @@ static int SFX(run)(const lto_scene* sc, uint64_t n_photons, uint64_t photon_off
     return 0;
 }
 
+#undef R_HG_SMALL_G
 #undef R_EPSILON
 #undef R_TRI_EPS
 #undef R_INF

@@ -14,8 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
-FN = dict(HG_PDF=0, HG_SAMPLE=1, ONB=2, DISK=3, COSINE_HEMI=4, REFLECT=5, BOUNDARY=6, SPIN=7)
-_FN_SHAPE = {0: (2, 1), 1: (2, 1), 2: (3, 6), 3: (2, 2), 4: (8, 4), 5: (6, 3), 6: (8, 5), 7: (5, 3)}
+FN = dict(HG_PDF=0, HG_SAMPLE=1, ONB=2, DISK=3, COSINE_HEMI=4, REFLECT=5, BOUNDARY=6, SPIN=7, HG_WALK=11)
+_FN_SHAPE = {0: (2, 1), 1: (2, 1), 2: (3, 6), 3: (2, 2), 4: (8, 4), 5: (6, 3), 6: (8, 5), 7: (5, 3), 11: (14, 2)}
 FX_SCALE = 2.0 ** 40
 VERTEX_DTYPE = np.dtype([("point", "<f8", 3), ("direction", "<f8", 3), ("g_norm", "<f8", 3), ("throughput", "<f8"),
                          ("pdf_pos", "<f8"), ("pdf_dir", "<f8"), ("kind", "<i4"), ("medium", "<i4"), ("step", "<u4"),
@@ -281,6 +281,11 @@ def rng_raw(seed, photon_id, count):
     lib().lto_rng_raw(C.c_uint64(seed), C.c_uint64(photon_id), C.c_uint32(count),
                       out.ctypes.data_as(C.POINTER(C.c_uint32)))
     return out
+
+
+def plant_cos0(on):
+    """Test hook: while on, every scattering of the oracle's walks deflects by exactly 90 degrees (lt_oracle.c)."""
+    lib().lto_plant_cos0(C.c_int(1 if on else 0))
 
 
 def conservation_residual(c):

@@ -75,6 +75,67 @@ SCENES = {
                                                       extra=(1.6, 0.0, 1.2, 0.0, 2.0, 0.0), start_medium=0)), 500, K, 0),
 }
 
+# ---------------------------------------------------------------- the edges of what lt_set_media accepts
+# 500 photons, K = 40, 16^3 grids.  Until these scenes existed the walk sampled Henyey-Greenstein by the quotient form for every
+# g != 0, which cancels as g -> 0: on the parent's oracle check C failed in t_g1e-6 (6346 of 7697 scatterings, worst 1.1e-10),
+# t_gneg1e-9 (all, 9.7e-8), t_g1e-12 (all, 7.2e-5) and in their cone and fluence twins -- exactly the scenes with |g| <= 1e-6.
+NE = 500
+
+
+def half_space(g, **kw):
+    return layered([(0.1, 10.0, g, 1.0)], [0.0, np.inf], **kw)
+
+
+def _cornell_cone(g):
+    """(i)'s source above (f)'s cone, whose medium gets the g: the mesh walk reads it from the medium table, not a layer record."""
+    prob = _cornell_with(dict(type=1, pos=(-1.0, -1.0, 0.0), dir=(0.6, 0.0, -0.8), extra=(1.6, 0.0, 1.2, 0.0, 2.0, 0.0),
+                              start_medium=0))
+    prob.media = [prob.media[0], (1.0, 5.0, g, 1.5)]
+    return prob
+
+
+SCENES.update({
+    # tiny g: the sampling's cancellation (fixed: hg_small_g below |g| = 2^-6); one on each side of the switch as well
+    "t_g1e-3": (lambda: half_space(1e-3), NE, K, 0),
+    "t_g1e-6": (lambda: half_space(1e-6), NE, K, 0),
+    "t_gneg1e-9": (lambda: half_space(-1e-9), NE, K, 0),
+    "t_g1e-12": (lambda: half_space(1e-12), NE, K, 0),
+    "t_g1e-6_cone": (lambda: _cornell_cone(1e-6), NE, K, 0),
+    "t_gneg1e-9_fluence": (lambda: half_space(-1e-9), NE, K, 1),
+    # extreme g: the CDF is ill-conditioned there (path_audit: C.cos, E.pdf_roundings).  g = +-0.999 under a vertical beam is
+    # left out: the reference alone takes the near-pole rule at 13 % / 18.5 % of the scatterings, above its 1 % cap
+    "x_g099": (lambda: half_space(0.99), NE, K, 0),
+    "x_g0999_tilted": (lambda: half_space(0.999, direction=TILT), NE, K, 0),
+    "x_gneg099": (lambda: half_space(-0.99), NE, K, 0),
+    # near-matched indices: Fresnel's differences of nearly equal products
+    "n_slab_1e-9_in_air": (lambda: layered([(0.1, 10.0, 0.9, 1.0 + 1e-9)], [0.0, 0.3]), NE, K, 0),
+    "n_two_layers_1e-7": (lambda: layered([(0.1, 10.0, 0.9, 1.4), (0.1, 10.0, 0.9, 1.4 * (1.0 + 1e-7))], [0.0, 0.1, 0.3],
+                                          n_below=1.4), NE, K, 0),
+    # a layer 1e-9 thick between two ordinary ones
+    "s_sliver": (lambda: layered([(0.1, 10.0, 0.9, 1.4), (0.1, 10.0, 0.9, 1.33), (0.1, 10.0, 0.9, 1.5)],
+                                 [0.0, 0.1, 0.1 + 1e-9, 0.3]), NE, K, 0),
+    # albedo -> 1 and -> 0
+    "w_albedo_to_1": (lambda: layered([(1e-9, 10.0, 0.5, 1.0)], [0.0, np.inf]), NE, K, 0),
+    "w_albedo_to_0": (lambda: layered([(10.0, 1e-9, 0.5, 1.0)], [0.0, np.inf]), NE, K, 0),
+    # mu_t = 1.01e5 in voxels of 1e-4
+    "m_dense": (lambda: layered([(1e3, 1e5, 0.9, 1.4)], [0.0, np.inf], voxel=1e-4), NE, K, 0),
+    # a beam 0.1 degrees off grazing
+    "z_grazing": (lambda: layered([(0.1, 10.0, 0.9, 1.4)], [0.0, 0.3], pos=(0.05, 0.05, 0.0),
+                                  direction=(float(np.sin(np.radians(89.9))), 0.0, float(np.cos(np.radians(89.9))))), NE, K, 0),
+})
+
+
+EDGE = frozenset(n for n in SCENES if n[:2] in ("t_", "x_", "n_", "s_", "w_", "m_", "z_"))
+
+
+def tol(name):
+    """The tolerances of the scene's audit (path_audit.TOL, or TOL_EDGE for the edge scenes)."""
+    return PA.TOL_EDGE if name in EDGE else PA.TOL
+
+
+def oracle_worst(name):
+    return PA.ORACLE_WORST_EDGE if name in EDGE else PA.ORACLE_WORST
+
 
 @functools.lru_cache(maxsize=None)
 def problem(name):
@@ -145,6 +206,29 @@ OCCURRED = {
     "h_slab_as_mesh": {"G": dict(reflected=1000, transmitted=5000, total_internal=500, left=100), "I": dict(weight0=500),
                        "A": dict(carried=5000, through_clear=2000)},
     "i_quad_facing_down": {"H": dict(n=500), "I": dict(capped=500), "G": dict(reflected=100, transmitted=400)},      # (the cone)
+    # the edge scenes (C last_medium: scatterings in the medium the scene is about)
+    "t_g1e-3": {"C": dict(axis=500, last_medium=5000)},
+    "t_g1e-6": {"C": dict(axis=500, last_medium=5000)},
+    "t_gneg1e-9": {"C": dict(axis=500, last_medium=5000)},
+    "t_g1e-12": {"C": dict(axis=500, last_medium=5000)},
+    "t_g1e-6_cone": {"C": dict(last_medium=1000), "G": dict(transmitted=400)},                     # (scatterings inside the cone)
+    "t_gneg1e-9_fluence": {"C": dict(axis=500, last_medium=5000), "J": dict(voxels_hit=1000)},
+    "x_g099": {"C": dict(ill_conditioned=15000, pole=1)},
+    "x_g0999_tilted": {"C": dict(ill_conditioned=15000)},
+    "x_gneg099": {"C": dict(ill_conditioned=4000, pole=1)},
+    # crossed = every transmission, those that leave the slab included.  500 photons cross a lone slab once each on entry
+    # (there the specular term, ((n - 1) / (n + 1))^2 = 2.5e-19, is the Fresnel event) and once on leaving, which is what F
+    # counts: 500, not the 1000 of the two-layer scene.  Reflected may be 0: R is 1e-19 and 1e-15 but for total reflection
+    "n_slab_1e-9_in_air": {"F": dict(crossed=500), "H": dict(specular=2.4e-19)},
+    # the two-layer scene: 557 transmissions from layer to layer (R = 6e-16 between 1.4 and 1.4 (1 + 1e-7), 1e-15 into the
+    # matched ambient below) and 496 exits, 1053 crossings (oracle and device alike); 1000 layer-to-layer ones would take more
+    # than the 500 photons every edge scene has
+    "n_two_layers_1e-7": {"F": dict(crossed=1000, transmitted=500)},
+    "s_sliver": {"A": dict(carried=1000), "F": dict(transmitted=1000)},
+    "w_albedo_to_1": {"I": dict(capped=100), "J": dict(deposits=9000)},
+    "w_albedo_to_0": {"E": dict(roulette_died=400, roulette_survived=50)},
+    "m_dense": {"F": dict(total_internal=50), "J": dict(voxels_hit=100, deposits=15000)},
+    "z_grazing": {"H": dict(specular=0.98), "F": dict(total_internal=500)},       # (normal incidence: 0.0278)
 }
 
 
@@ -155,7 +239,7 @@ def check_result(res, name, worst_allowed=None):
         assert r["violations"] == 0, "%s, check %s: %d violations\n%s" % (name, k, r["violations"], report(res))
         assert r["declined"] == 0, "%s, check %s: %d decisions too close to call" % (name, k, r["declined"])
         for m, w in r["worst"].items():
-            assert w <= PA.TOL[m], (name, m, w)
+            assert w <= tol(name)[m], (name, m, w)
             if worst_allowed is not None and m in worst_allowed:
                 assert w <= worst_allowed[m], "%s: the oracle's %s = %.3g exceeds the recorded %.3g" % (name, m, w, worst_allowed[m])
     scat = res["C"]["n"]

@@ -33,9 +33,47 @@ to a power of ten, at most 1e-8; path_audit.ORACLE_WORST / TOL), and the kernels
     I.sum (ratio to bound)  0.083      1           0.019
     J.voxel (ratio)         0.255      1           0.494
 
+The same over the EDGE scenes (path_audit_scenes.EDGE: tiny and extreme g, near-matched indices, a sliver layer, albedo -> 1
+and -> 0, mu_t = 1e5, a grazing beam; 500 photons each, seed 97), which have a table of their own (path_audit.ORACLE_WORST_EDGE /
+TOL_EDGE; C.cos, E.pdf_roundings, E.weight_in exist only there).  Before the walk sampled |g| < 2^-6 by hg_small_g, check C
+failed on the oracle in exactly the scenes with |g| <= 1e-6: t_g1e-6 6346 of 7697 scatterings (worst 1.1e-10), t_gneg1e-9 and
+its fluence twin 7695 (9.7e-8), t_g1e-12 all 7697 (7.2e-5), t_g1e-6_cone 1576 of the 1918 in the cone (1.1e-10); every other
+edge scene passed before and after.
+
+    measure                 oracle     tolerance   kernels (MI355X)
+    A.tau                   1.03e-11   1e-09       6.28e-12
+    B.perp                  4.26e-16   1e-13       4.27e-16
+    B.unit                  2.93e-12   1e-10       1.78e-12
+    C.cdf                   6.16e-13   1e-11       4.51e-13
+    C.cos                   1.81e-16   1e-14       1.56e-16
+    D.azimuth               5.29e-13   1e-10       3.21e-13
+    E.pdf                   3.40e-12   1e-10       2.50e-12
+    E.pdf_roundings         1.11       100         0.372
+    E.weight                1.18e-16   1e-14       1.18e-16
+    E.weight_in             7.61e-17   1e-14       7.61e-17
+    F.R                     5.03e-13   1e-11       2.64e-13
+    F.plane                 6.66e-17   1e-14       6.90e-17
+    F.reflect               0          0           0
+    F.snell                 5.76e-14   1e-12       3.02e-14
+    G.R                     2.37e-14   1e-11       5.03e-14
+    G.inside                0          1e-14       0
+    G.nearest               7.63e-15   1e-12       3.14e-15
+    G.normal                6.29e-17   1e-14       6.29e-17
+    G.plane                 4.45e-16   1e-14       3.05e-16
+    G.plane_of_incidence    1.06e-16   1e-14       8.76e-17
+    G.reflect               2.95e-16   1e-14       2.42e-16
+    G.snell                 5.47e-14   1e-12       2.03e-14
+    H.dir                   1.01e-15   1e-13       1.12e-15
+    H.pdf                   3.80e-16   1e-14       3.33e-16
+    H.point                 1.92e-16   1e-14       1.92e-16
+    H.weight                7.06e-17   1e-14       7.06e-17
+    I.sum                   0.095      1           0.0433
+    J.voxel                 0.247      1           0.247
+
 Conditions, not measurements (met by the oracle and by the kernels): no reflect / transmit decision within 1e-12 of R, no
 deposit within 1e-9 voxel of a face (cap 1e-4 of the deposits), the near-pole approximation at 4 of 64 587 scatterings in
-scene (a) (cap 1 %), no triangle hidden by the walk's 1e-6 / 1e-7 rules, no leak.
+scene (a) (cap 1 %; edge scenes: 84 of 18 825 at g = 0.99, 31 of 4876 at g = -0.99, 0 of 19 000 at g = 0.999 under the tilted beam),
+no triangle hidden by the walk's 1e-6 / 1e-7 rules, no leak.
 """
 import numpy as np
 import pytest
@@ -78,7 +116,7 @@ def device_draws(ctx, name, first=64):
 @pytest.mark.parametrize("name", list(PS.SCENES))
 def test_device_paths_follow_the_textbook_laws(ctx, name):
     g, c, v, cnt, info = device_capture(ctx, name)
-    res = PA.audit(PS.plain(PS.problem(name), PS.SCENES[name][3]), device_draws(ctx, name), v, cnt, c, g)
+    res = PA.audit(PS.plain(PS.problem(name), PS.SCENES[name][3]), device_draws(ctx, name), v, cnt, c, g, tol=PS.tol(name))
     print(name + "\n" + PS.report(res))
     PS.check_result(res, name)
     if name == "g_sphere_march":
